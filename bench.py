@@ -39,6 +39,23 @@ Workloads (--workload):
 Multi-GPU: one process per GPU.  `python bench.py --gpus N` without a torchrun environment
 starts `torch.distributed.run` with N processes itself (before touching the GPU) and exits with
 its code; under torchrun, WORLD_SIZE must equal --gpus.
+
+A plain run does what the headline needs and no more: set-up, --warmup steps, --steps timed steps,
+the results of the last step back on the host (iterations, statuses, the roofline arithmetic) and
+the JSON line.  --full adds everything that takes runs of its own: the CPU baseline (oracle) and
+the parity check against it, the PCIe-inclusive end-to-end steps (serial and pipelined), the
+candidate selection (config3) and config5's untimed replay with its per-step statistics, chain
+parity and CPU baseline; without it those fields of the line are null.
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the timed path receives
+it from impc_batch_get, per pattern bucket (in launch order) as float64 .npy files:
+  bucketNN_info.npy  [B][8]   every QP's info record (the INFO_DTYPE fields, in order)
+  bucketNN_rows.npy  [r]      the QPs whose x and y are kept (all, or a fixed seeded sample that
+                              keeps the whole dump under 64 MB), ascending
+  bucketNN_x.npy     [r][n]   primal solutions of those QPs
+  bucketNN_y.npy     [r][m]   dual solutions of those QPs
+(ranks > 0 of a multi-GPU run prefix their files with rankR_).  The workloads are seeded, so two runs
+with the same arguments solve identical inputs.
 """
 import argparse
 import json
@@ -140,6 +157,30 @@ def make_batch(impc, ctx, bk, settings, full_values, profile, queue_weight=None)
         b.set_queue_order(impc.QUEUE_LONGEST_FIRST, queue_weight)
     b.set_profiling(profile)
     return b, nvar
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: all files of all ranks together (the limit is 64 MB)
+DUMP_SEED = 65536
+
+
+def dump_outputs(path, results, rank=0, world=1):
+    """--dump-outputs: the last timed step's (x, y, info) per bucket as float64 .npy files (module
+    docstring).  Every QP's info record is kept; x and y of a seeded sample of QPs, the same for the
+    same workload, sized so that everything stays within DUMP_BUDGET_BYTES / world."""
+    os.makedirs(path, exist_ok=True)
+    pre = f"rank{rank}_" if rank else ""
+    total = sum(x.shape[0] for x, _, _ in results)
+    info_bytes = sum(8 * len(info.dtype.names) * info.shape[0] for _, _, info in results)
+    row_bytes = max(8 * (x.shape[1] + y.shape[1] + 1) for x, y, _ in results)
+    keep = max(0, DUMP_BUDGET_BYTES // world - info_bytes) // row_bytes  # QPs whose x, y fit
+    rng = np.random.default_rng(DUMP_SEED)
+    for i, (x, y, info) in enumerate(results):
+        B = x.shape[0]
+        r = B if keep >= total else min(B, keep * B // total)
+        rows = np.arange(B) if r == B else np.sort(rng.choice(B, size=r, replace=False))
+        rec = np.stack([info[k].astype(np.float64) for k in info.dtype.names], axis=1)
+        for name, a in (("info", rec), ("rows", rows.astype(np.float64)), ("x", x[rows]), ("y", y[rows])):
+            np.save(os.path.join(path, f"{pre}bucket{i:02d}_{name}.npy"), np.ascontiguousarray(a, np.float64))
 
 
 def end_to_end(impc, ctx, batches, args, grouped):
@@ -262,6 +303,14 @@ def main():
     ap.add_argument("--instances", type=int, default=8192,
                     help="config3 / config5: planning instances of the job (x8 hypotheses)")
     ap.add_argument("--total-qps", type=int, default=262144, help="config4: QPs of the whole job")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: CPU baseline + parity vs the oracle, end-to-end "
+                         "(PCIe-inclusive) steps, candidate selection, config5's replay (module docstring); the "
+                         "options --cpu-sample, --cpu-threads, --cpu-all-cores, --e2e-steps and --receding-replay "
+                         "shape those parts and have no effect without --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results (x, y, info per bucket) as float64 "
+                         ".npy files into DIR (module docstring)")
     ap.add_argument("--cpu-sample", type=int, default=8192, help="QPs solved by the CPU baseline (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=16,
                     help="CPU baseline threads (the GPU box's CPU share per GPU is 16)")
@@ -286,6 +335,10 @@ def main():
                     help="ship every QP's full CSC values (default: shared P / dynamics / box values, "
                          "per-QP obstacle rows, impc_batch_set_values_shared)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: the timed steps and the line only
+        args.cpu_sample = args.cpu_all_cores = args.e2e_steps = args.receding_replay = 0
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(relaunch(args.gpus, sys.argv[1:]))
@@ -416,13 +469,16 @@ def main():
         alg_flops += algorithmic_flops(pat["n"], pat["m"], int(pat["Ap"][-1]), bk["N"], info["iter"])
     iters_all = np.concatenate(iters_all)
     status_all = np.concatenate(status_all)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, results, rank, world)
 
     sel = None
     if args.workload == "config3":
-        # device-side candidate scoring + selection of every instance's replan (SURVEY.md 8f row 1,
-        # mpcPlanner.cpp:771-887), on the solutions still in HBM; timed on its own
-        sel = select_candidates(impc, scenarios, ctx, buckets, dict((bk["K"], b) for bk, b in batches),
-                                pd_params=bks[0]["params"])
+        if args.full:
+            # device-side candidate scoring + selection of every instance's replan (SURVEY.md 8f row 1,
+            # mpcPlanner.cpp:771-887), on the solutions still in HBM; timed on its own
+            sel = select_candidates(impc, scenarios, ctx, buckets, dict((bk["K"], b) for bk, b in batches),
+                                    pd_params=bks[0]["params"])
         if comm is not None and not args.no_allgather and not gather_in_step:  # costs to every rank
             comm.gather_info([b for _, b in batches], max_qps, recv.ptr)
     gathered = None
@@ -547,6 +603,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": ms_per_step,
         "p50_latency_ms": qp_lat["p50"] if qp_lat else None,
         "step_latency_ms": ms_per_step,
