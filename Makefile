@@ -34,12 +34,13 @@ EMU     := $(HARNDIR)/libwave_emu.so
 EMU64   := $(HARNDIR)/libwave_emu64.so
 SHIMT   := $(HARNDIR)/shim_test
 REPLANX := $(HARNDIR)/replan_example
+DETECTH := $(HARNDIR)/libdetect_harness.so
 
 .PHONY: all lib oracle harness prof variant clean
 all: lib oracle harness
 lib: $(LIB)
 oracle: $(ORACLE)
-harness: $(HARNESS) $(EMU) $(EMU64) $(SHIMT) $(REPLANX)
+harness: $(HARNESS) $(EMU) $(EMU64) $(SHIMT) $(REPLANX) $(DETECTH)
 
 $(LIBDIR)/impc_qp.o: $(CSRC)/impc_qp.hip $(CSRC)/admm_core.hpp $(CSRC)/symbolic.hpp $(CSRC)/mpc_wave.hpp \
 		$(CSRC)/mpc_structure.hpp $(CSRC)/select.hpp $(CSRC)/mpc_build.hpp $(CSRC)/mpc_qp_internal.hpp \
@@ -54,7 +55,8 @@ prof: $(PROFLIB)
 $(LIBDIR)/impc_qp_prof.o: $(CSRC)/impc_qp.hip $(CSRC)/admm_core.hpp $(CSRC)/symbolic.hpp $(CSRC)/mpc_wave.hpp \
 		$(CSRC)/mpc_structure.hpp $(CSRC)/select.hpp $(CSRC)/mpc_build.hpp $(CSRC)/mpc_qp_internal.hpp \
 		$(CSRC)/fanout.hpp $(CSRC)/predict.hpp $(CSRC)/comm.hpp $(CSRC)/reftraj.hpp $(ROOT)/include/impc_qp.h $(ROOT)/include/impc_select.h $(ROOT)/include/impc_mpc.h \
-		$(ROOT)/include/impc_fanout.h $(ROOT)/include/impc_predict.h
+		$(ROOT)/include/impc_fanout.h $(ROOT)/include/impc_predict.h $(ROOT)/include/impc_detect.h \
+		$(CSRC)/detect.hpp $(CSRC)/detect_gate.hpp
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) $(call IDFLAGS,-prof) -DIMPC_SECTION_PROF -c $< -o $@
 $(PROFLIB): $(LIBDIR)/impc_qp_prof.o $(LIBDIR)/replan_run.o $(LIBDIR)/symbolic.o $(LIBDIR)/mpc_qp.o $(LIBDIR)/mpc_structure.o $(LIBDIR)/minsnap.o
@@ -120,6 +122,11 @@ $(REPLANX): $(ROOT)/tests/native/replan_example.cpp $(ROOT)/include/impc_qp.h $(
 	@mkdir -p $(HARNDIR)
 	$(CXX) -O2 -std=c++17 -Wall -I$(ROOT)/include $< -L$(LIBDIR) -limpc_qp \
 		-Wl,-rpath,'$$ORIGIN/../../../intent-mpc_amd/lib' -o $@
+
+# the range gate's predicate (csrc/detect_gate.hpp) compiled for the host
+$(DETECTH): $(ROOT)/tests/native/detect_harness.cpp $(CSRC)/detect_gate.hpp
+	@mkdir -p $(HARNDIR)
+	$(HIPCC) -x hip --offload-host-only -std=c++17 -O2 -fPIC -shared -ffp-contract=off $< -o $@
 
 # kernel experiments (tools/ only): make variant V=name DEFS="-DX=1" -> lib/libimpc_qp_<name>.so,
 # selected at run time with IMPC_LIB_VARIANT=<name>

@@ -26,6 +26,7 @@
 #include "../../include/impc_mpc.h"
 #include "../../include/impc_fanout.h"
 #include "../../include/impc_predict.h"
+#include "../../include/impc_detect.h"
 #include "../../include/impc_comm.h"
 #include "../../include/impc_replan.h"
 #include "lib_internal.hpp"
@@ -2465,6 +2466,9 @@ int impc_copy_to_host(impc_ctx ctx, void *dst, const void *src, int64_t bytes) {
 
 // ---------------------------------------------------------------- obstacle intent probabilities
 #include "predict.hpp"
+
+// ---------------------------------------------------------------- detector track store, range gate
+#include "detect.hpp"
 
 // ---------------------------------------------------------------- on-device MPC -> QP assembly
 #include "mpc_build.hpp"

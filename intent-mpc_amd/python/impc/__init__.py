@@ -267,6 +267,8 @@ EXPORTED = [
     "impc_replan_view_device", "impc_replan_shape", "impc_replan_advance_device", "impc_batch_follow_plan_device",
     "impc_copy_rows_device", "impc_batch_update_matrices", "impc_batch_update_matrices_device",
     "impc_batch_get_persistent",
+    "impc_tracks_create", "impc_tracks_destroy", "impc_tracks_push_device", "impc_tracks_reset",
+    "impc_detect_gather_device", "impc_detect_gather",  # bound in impc.perception
 ]
 
 

@@ -333,18 +333,12 @@ def dynus_path():
     return np.array(rows)
 
 
-def live_loop(instances, K, replans, N=30, seed=4100, params=None):
-    """R chained replans of I planning instances flying the reference's benchmark path, each
-    instance's copy of the path shifted sideways / up by a seeded offset, K dynamic obstacles per
-    instance crossing it at constant velocity (re-predicted every 0.1 s replan by the predictor's
-    four kinematic intent models, predict_intents), constant intent probabilities per obstacle.
-    The vehicle starts at rest at its path's first point on its first plan (firstTime_).
-    Returns dict(paths [I][P][3], pos0 / vel0 [I][3], pred_pos [R][I][K][4][L][3] (the predictions
-    handed to replan r), pred_size [I][K][4][L][3], prob [I][K][4], dyn_cur [R][I][K][3], size,
-    params, pd, N, K, L)."""
+def _live_setup(instances, K, N, seed, params):
+    """The live loop's seeded world: every instance's copy of the benchmark path, its start state and
+    its K obstacles' start positions, constant velocities and intent probabilities."""
     p, pd = params if params is not None else mpc_params(horizon=N)
     rng = np.random.default_rng(seed)
-    I, ts = instances, pd["ts"]
+    I = instances
     base = dynus_path()
     off = np.stack([np.zeros(I), rng.uniform(-1.5, 1.5, I), rng.uniform(-0.5, 0.5, I)], axis=1)
     paths = base[None, :, :] + off[:, None, :]
@@ -359,6 +353,20 @@ def live_loop(instances, K, replans, N=30, seed=4100, params=None):
     hdg = np.where(side < 0, 0.5 * math.pi, -0.5 * math.pi) + rng.uniform(-1.0, 1.0, (I, K))
     obv = np.stack([spd * np.cos(hdg), spd * np.sin(hdg), np.zeros((I, K))], axis=2)
     prob = rng.dirichlet(np.full(4, 2.0), size=(I, K))
+    return p, pd, paths, pos0, vel0, obp, obv, prob
+
+
+def live_loop(instances, K, replans, N=30, seed=4100, params=None):
+    """R chained replans of I planning instances flying the reference's benchmark path, each
+    instance's copy of the path shifted sideways / up by a seeded offset, K dynamic obstacles per
+    instance crossing it at constant velocity (re-predicted every 0.1 s replan by the predictor's
+    four kinematic intent models, predict_intents), constant intent probabilities per obstacle.
+    The vehicle starts at rest at its path's first point on its first plan (firstTime_).
+    Returns dict(paths [I][P][3], pos0 / vel0 [I][3], pred_pos [R][I][K][4][L][3] (the predictions
+    handed to replan r), pred_size [I][K][4][L][3], prob [I][K][4], dyn_cur [R][I][K][3], size,
+    params, pd, N, K, L)."""
+    p, pd, paths, pos0, vel0, obp, obv, prob = _live_setup(instances, K, N, seed, params)
+    I, ts = instances, pd["ts"]
     L = PRED_STEPS + 1
     pred = np.empty((replans, I, K, 4, L, 3))
     for r in range(replans):
@@ -367,3 +375,27 @@ def live_loop(instances, K, replans, N=30, seed=4100, params=None):
     pred_size = np.ascontiguousarray(np.broadcast_to(size, (I, K, 4, L, 3)))
     return dict(paths=paths, pos0=pos0, vel0=vel0, pred_pos=pred, pred_size=pred_size, prob=prob,
                 dyn_cur=np.ascontiguousarray(pred[:, :, :, FORWARD, 0, :]), size=size, params=p, pd=pd, N=N, K=K, L=L)
+
+
+def live_world(instances, M, replans, pushes_per_replan=3, N=30, seed=4100, params=None):
+    """The live loop with the detector in it: live_loop's paths and obstacle placement (the same
+    seed gives the same paths, start states and obstacles), each instance with its own world of M
+    obstacles moving at constant velocity, as the boxes the detector's history timer pushes -- it
+    runs every 0.033 s against the 0.1 s replan (fakeDetector.cpp:69), hence three pushes per
+    replan.  Push n = r * pushes + q (q = 0 .. pushes - 1) belongs to replan r and is taken at the
+    time (n - (pushes - 1)) ts / pushes, so the newest entry at replan r is the obstacle at r ts,
+    where live_loop has it.  Returns dict(paths, pos0 / vel0 [I][3], world_pos [R * pushes][I][M][3],
+    world_vel / world_size [I][M][3] (constant), map (origin, res, dims) + occ: an empty occupancy
+    grid around the flight for the predictor (1 m voxels; outside it counts as occupied), params,
+    pd, N, M, L)."""
+    p, pd, paths, pos0, vel0, obp, obv, _ = _live_setup(instances, M, N, seed, params)
+    ts, P = pd["ts"], int(pushes_per_replan)
+    t = (np.arange(replans * P) - (P - 1)) * (ts / P)
+    world_pos = obp[None] + obv[None] * t[:, None, None, None]
+    lo = np.floor(np.minimum(paths.min(axis=(0, 1)), world_pos.min(axis=(0, 1, 2))) - 20.0)
+    hi = np.ceil(np.maximum(paths.max(axis=(0, 1)), world_pos.max(axis=(0, 1, 2))) + 20.0)
+    dims = [int(v) for v in hi - lo]
+    return dict(paths=paths, pos0=pos0, vel0=vel0, world_pos=world_pos, world_vel=obv,
+                world_size=np.ascontiguousarray(np.broadcast_to(np.full(3, 0.8), obp.shape)),
+                map=dict(origin=lo.tolist(), res=1.0, dims=dims), occ=np.zeros(dims, np.uint8), params=p, pd=pd, N=N,
+                M=M, L=PRED_STEPS + 1)

@@ -22,7 +22,18 @@ replans its own (the selection is per instance: no exchange inside a replan), a 
 max over ranks bound each replan's time, and the last replan's per-instance records
 (impc.distributed.replan_records) reach every rank.  The rate is all ranks' instances over that
 time.  The same loop at small I is checked replan by replan against the restatements in
-tests/test_live_loop.py; the rank split in tests/test_distributed.py."""
+tests/test_live_loop.py; the rank split in tests/test_distributed.py.
+
+--detector [--range 30.0] [--hist 100]: the detector in the loop instead of baked predictions
+(scenarios.live_world; defaults from fake_detector_param.yaml color_distance / history_size).  Every
+instance has its own world of --world-obstacles M obstacles; per replan three history pushes
+(impc_tracks_push_device: histCB's 0.033 s timer), ONE impc.perception.DeviceTick (range gate ->
+intent probabilities -> predicted trajectories -> makePlanWithPred with num_pred = the gate's K_i)
+and the vehicle following its plan, all queued on the context stream.  K_i changes only when an
+obstacle crosses the sensor range.  The line gains, per replan, the histogram of K_i, the count of
+truncated instances (more in range than the K slots), the branch counts and the device times of the
+gate, the two predictor kernels and the replan (the context's step timer).  One GPU.  The same tick
+at small I is checked replan by replan in tests/test_tick.py."""
 import argparse
 import json
 import os
@@ -47,6 +58,92 @@ def relaunch(n, argv):
     return subprocess.call(cmd, env=env)
 
 
+def detector_loop(a):
+    import impc
+    from impc import perception as P
+    from impc import scenarios
+    from impc.replan import DeviceReplan
+    I, K, R, N, M, PUSHES = a.instances, a.obstacles, a.replans, a.horizon, a.world_obstacles, 3
+    t0 = time.time()
+    w = scenarios.live_world(I, M, R, pushes_per_replan=PUSHES, N=N, seed=4100)
+    gen_s = time.time() - t0
+    p, pd, L = w["params"], w["pd"], w["L"]
+    ctx = impc.Context(0)
+    rp = DeviceReplan(ctx, p, pd, I, K, L, impc.default_settings(verbose=0))
+    paths = impc.ReferencePaths(ctx, list(w["paths"]), pd["ts"], N)
+    tracks = P.Tracks(ctx, I, M, a.hist)
+    tick = P.DeviceTick(ctx, rp, tracks, P.detect_params(a.range, P.FOV_ALL, (0.0, 0.0, 0.0), K), occ=w["occ"],
+                        omap=w["map"])
+    Dv = impc.DeviceArray
+    c = np.ascontiguousarray
+    pos_d, vel_d, xref_d = Dv(ctx, c(w["pos0"])), Dv(ctx, c(w["vel0"])), Dv(ctx, (I, N, 8))
+    world_d, wvel_d, wsize_d = Dv(ctx, c(w["world_pos"])), Dv(ctx, c(w["world_vel"])), Dv(ctx, c(w["world_size"]))
+    step = world_d.nbytes // (R * PUSHES)
+    walls, branches, k_hist, truncated = [], [], [], []
+    for r in range(R):
+        ctx.synchronize()
+        t = time.perf_counter()
+        for q in range(PUSHES):
+            tracks.push_device(world_d.ptr + (r * PUSHES + q) * step, wvel_d.ptr, wsize_d.ptr)
+        paths.xref_device(pos_d.ptr, xref_d.ptr)
+        ctx.timer_mark()
+        tick.gather(pos_d.ptr)
+        ctx.timer_mark()
+        ctx.timer_mark()
+        tick.intent()
+        ctx.timer_mark()
+        ctx.timer_mark()
+        tick.trajectories()
+        ctx.timer_mark()
+        ctx.timer_mark()
+        tick.plan(pos_d.ptr, vel_d.ptr, xref_d.ptr)
+        ctx.timer_mark()
+        rp.advance_device(pd["ts"], pos_d.ptr, vel_d.ptr)
+        ctx.synchronize()
+        walls.append(time.perf_counter() - t)
+        st = rp.stats()
+        branches.append([int(st["fanout"]), int(st["single_first"]), int(st["single_current"])])
+        num, inr = tick.gate.num.get(), tick.gate.in_range.get()
+        k_hist.append(np.bincount(num, minlength=K + 1).tolist())
+        truncated.append(int((inr > K).sum()))
+    ms = ctx.timer_read(max_pairs=4 * R).reshape(R, 4)  # per replan: gate, intent probabilities, trajectories, replan
+    last = rp.results(values=False)
+    its = np.concatenate([s["info"]["iter"] for s in last["shapes"].values()])
+    sts = np.concatenate([s["info"]["status_val"] for s in last["shapes"].values()])
+    _, _, _, valid = rp.plans()
+    wl = np.array(walls)
+    fan = wl[1:]
+    med = lambda v: float(np.median(v))  # noqa: E731
+    print(json.dumps({
+        "workload": f"live loop with the detector: {I} instances on ref_trajectory_dynus_benchmark.txt, N={N}, worlds of "
+                    f"{M} obstacles, sensor range {a.range} m, K={K} slots, history {a.hist}, {R} chained replans "
+                    f"({PUSHES} history pushes + getXRef + gate + intent probabilities + predicted trajectories + "
+                    f"makePlanWithPred + follow plan 0.1 s per replan)",
+        "instances": I, "replans": R, "n_gpus": 1, "first_replan_s": float(wl[0]), "fanout_replan_s": fan.tolist(),
+        "fanout_replan_s_median": med(fan), "replans_per_s": float(I / med(fan)),
+        "device_ms_median": {"gate": med(ms[1:, 0]), "intent_prob": med(ms[1:, 1]), "predict_traj": med(ms[1:, 2]),
+                             "replan": med(ms[1:, 3])},
+        "device_ms": {"gate": ms[:, 0].tolist(), "intent_prob": ms[:, 1].tolist(), "predict_traj": ms[:, 2].tolist(),
+                      "replan": ms[:, 3].tolist()},
+        "k_hist": k_hist, "truncated": truncated, "branches": branches,
+        "last_replan_rank0": {"qps": int(its.size), "mean_iter": float(its.mean()), "p50_iter": float(np.median(its)),
+                              "max_iter": int(its.max()),
+                              "status_counts": {str(int(k)): int(v) for k, v in zip(*np.unique(sts, return_counts=True))},
+                              "shapes": {str(k): int(s["x"].shape[0]) for k, s in last["shapes"].items()}},
+        # QPs that ran all of settings.max_iter iterations, whatever status the final check gave them
+        "at_iter_cap_last": int((its >= rp.settings.max_iter).sum()),
+        "qp_solves_per_s_rank0": float(its.size / med(fan)), "valid_plans": int(valid.sum()),
+        "ref_start_idx_mean": float(paths.last_idx().mean()), "gen_s": gen_s,
+        "build_id": impc.lib.impc_build_id().decode()}), flush=True)
+    for d in (pos_d, vel_d, xref_d, world_d, wvel_d, wsize_d):
+        d.free()
+    tick.close()
+    tracks.close()
+    paths.close()
+    rp.close()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--instances", type=int, default=8192)
@@ -56,7 +153,15 @@ def main():
     ap.add_argument("--mixed-k", action="store_true", help="per-instance obstacle counts K_i in 0..K per replan")
     ap.add_argument("--statics", type=int, default=0, help="static obstacles per instance (num_static)")
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--detector", action="store_true", help="gate + predictor + replan per tick (DeviceTick)")
+    ap.add_argument("--range", type=float, default=30.0, help="--detector: sensor range (color_distance)")
+    ap.add_argument("--hist", type=int, default=100, help="--detector: history entries per track (history_size)")
+    ap.add_argument("--world-obstacles", type=int, default=8, help="--detector: obstacles M in every instance's world")
     a = ap.parse_args()
+    if a.detector:
+        if a.gpus != 1 or a.mixed_k or a.statics:
+            sys.exit("live_loop.py: --detector runs on one GPU, without --mixed-k / --statics")
+        return detector_loop(a)
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(relaunch(a.gpus, sys.argv[1:]))
     import impc  # noqa: E402  (after a possible relaunch: nothing touched the GPU before it)
