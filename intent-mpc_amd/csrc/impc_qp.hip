@@ -220,6 +220,14 @@ __global__ __launch_bounds__(kBlock) void k_update_bounds(impc::DevSym sy, impc:
 // Team policy of mpc_wave.hpp on gfx950: one QP per workgroup of NL threads (NL/64 wavefronts);
 // LDS exchange + workgroup barrier, readlane broadcast inside a wavefront, butterfly reductions
 // inside a wavefront combined across wavefronts through LDS in a fixed order (bitwise uniform).
+// IMPC_LCOMB (the product since round 7; 0: A/B variants only): the team reductions' combine across
+// wavefronts in one lane per value instead of in every lane.  The termination check reduces 17
+// maxima and 2 sums; combined in every lane that was 76 LDS reads and 57 three-instruction maxima
+// per lane and check, all 256 lanes computing the same 19 numbers (config 3: 210.35 / 210.35 ->
+// 206.83 / 206.78 ms per launch, identical outputs; profiles/r07/README.md)
+#ifndef IMPC_LCOMB
+#define IMPC_LCOMB 1
+#endif
 template <int NL>
 struct GpuTeam {
     double *red;  // >= NL/64 doubles of LDS
@@ -377,6 +385,28 @@ struct GpuTeam {
         }
         if ((threadIdx.x & 63) == 0) _Pragma("unroll") for (int k = 0; k < KS; k++) red[w * KT + KM + k] = sm[k];
         __syncthreads();
+#if IMPC_LCOMB
+        // Combine across wavefronts in one lane per value instead of every lane combining all KT:
+        // lane k of each wavefront takes value k's NL / 64 partials in wavefront order, as the
+        // every-lane form below does (the same bits), and v_readlane hands each result to the whole
+        // wavefront in scalar registers -- so the check's record (WaveQP::Info), live from one check
+        // to the output, holds no per-lane registers either.  Every caller is team-wide code (the
+        // barriers), so all 64 lanes are active here.
+        if constexpr (NL > 64) {
+            static_assert(KT <= 64, "one lane per reduced value");
+            const int l = (int)threadIdx.x & 63, k = l < KT ? l : 0;
+            double r = red[k];
+            for (int u = 1; u < NL / 64; u++) {
+                const double o = red[u * KT + k];
+                const double m = vmax(r, o), a = r + o;
+                r = k < KM ? m : a;
+            }
+            _Pragma("unroll") for (int j = 0; j < KM; j++) mx[j] = bcast(r, j);
+            _Pragma("unroll") for (int j = 0; j < KS; j++) sm[j] = bcast(r, KM + j);
+            __syncthreads();
+            return;
+        }
+#endif
         _Pragma("unroll") for (int k = 0; k < KM; k++) {
             double r = red[k];
             for (int u = 1; u < NL / 64; u++) r = vmax(r, red[u * KT + k]);
