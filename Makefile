@@ -65,7 +65,8 @@ $(PROFLIB): $(LIBDIR)/impc_qp_prof.o $(LIBDIR)/replan_run.o $(LIBDIR)/symbolic.o
 # the batched makePlanWithPred (include/impc_replan.h impc_replan_*): host orchestration + small
 # kernels over the library's own entry points
 $(LIBDIR)/replan_run.o: $(CSRC)/replan_run.hip $(CSRC)/lib_internal.hpp $(ROOT)/include/impc_replan.h \
-		$(ROOT)/include/impc_qp.h $(ROOT)/include/impc_mpc.h $(ROOT)/include/impc_fanout.h $(ROOT)/include/impc_select.h
+		$(ROOT)/include/impc_qp.h $(ROOT)/include/impc_mpc.h $(ROOT)/include/impc_fanout.h $(ROOT)/include/impc_select.h \
+		$(ROOT)/include/impc_comm.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -1,7 +1,10 @@
 /*
  * impc_comm.h -- multi-GPU plumbing of the batched solver: an RCCL communicator
- * over xGMI for the one exchange the path has (every rank's per-QP cost records to every rank,
- * for hypothesis selection), and device-side step timing.
+ * over xGMI for the two exchanges the path has, both one ncclAllGather of fixed-size records on
+ * the solver's stream -- every rank's per-QP cost records to every rank (impc_comm_gather_info,
+ * the raw-QP path) and every rank's per-instance replan records, each vehicle's chosen plan
+ * included, to every rank after a replan (impc_replan_gather, include/impc_replan.h) -- and
+ * device-side step timing.
  *
  * The reference has no multi-process path: mpcPlanner::makePlanWithPred solves its candidates
  * serially in one thread (mpcPlanner.cpp:609-628).  The batched replacement shards planning

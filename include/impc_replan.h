@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include "impc_qp.h"
 #include "impc_mpc.h"
+#include "impc_comm.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -160,7 +161,9 @@ int impc_replan_get_stats(impc_replan rp, impc_replan_stats *out);
  * num_obs [I] (fan-out: K_i; single solve: the dynamic-obstacle count of its QP = its shape, except
  * a first plan with num_static > 0: shape K + 2), slot_row [I][6] (fan-out: the row of slot s in
  * shape K_i (s < 4) or K_i + 1 (s >= 4); single solve: its row in its shape at [0]; -1
- * elsewhere), shape [I] (the shape of the instance's single solve; fan-out: K_i). */
+ * elsewhere), shape [I] (the shape of the instance's single solve; fan-out: K_i), weighted [I][6]
+ * (evaluateTraj's weighted score of every candidate of the last run's selection, getIntentComb
+ * order; NaN for a candidate that was not scored; unwritten before the first run). */
 typedef struct {
     double *plan_x, *plan_states;
     int32_t *prev_count;
@@ -168,6 +171,7 @@ typedef struct {
     int32_t *best_cand, *ob_idx, *cand_type, *cand_slot;
     int32_t *num_obs, *slot_row;
     int32_t *shape;
+    double *weighted;
 } impc_replan_view;
 int impc_replan_view_device(impc_replan rp, impc_replan_view *out);
 
@@ -183,6 +187,62 @@ int impc_replan_view_device(impc_replan rp, impc_replan_view *out);
 int impc_replan_shape(impc_replan rp, int32_t obstacles, impc_batch *batch, int64_t *count, const int32_t **row_inst,
                       const int8_t **row_code, const double **Px, const double **q, const double **Ax,
                       const double **l, const double **u);
+
+/* ======================================================================================
+ * What a replan decided, per planning instance, as one device-side record: the exchange of the
+ * multi-GPU replan (every rank's records to every rank; the reference's caller needs each vehicle's
+ * plan every 10 Hz tick, mpcNavigation.cpp:294-349).  A fixed 64-byte header, followed by
+ * plan_steps (P, 0 <= P <= N) stage states of the instance's committed plan, plan_states[inst]
+ * [0..P)[8] copied bit for bit: one record is 64 + 64 P bytes, a rank's block is its records back
+ * to back with no trailer.  An instance that kept its previous plan carries that plan (what the
+ * vehicle goes on following).  Every field is a copy of a value the device holds; nothing is summed
+ * or rounded.
+ *
+ * "The instance's QP" of status / iter / obj / pri_res / dua_res: the single solve of a
+ * single-solve instance, whether or not solveTraj succeeded (the status says why valid is 0); the
+ * selected candidate's QP of a fan-out instance with best_cand >= 0 (cand_slot -> slot_row -> shape
+ * K_i or K_i + 1); none for a fan-out instance without a selection -- the five fields and score
+ * stay zero.
+ * ====================================================================================== */
+typedef struct {
+    int32_t rank;        /* the rank that planned this instance                               off 0 */
+    int32_t inst;        /* global instance id = inst_base + local index                          4 */
+    int8_t branch;       /* IMPC_REPLAN_* of the last run                                         8 */
+    int8_t valid;        /* the last run's validTraj                                              9 */
+    int8_t first_time;   /* firstTime_ after the commit                                          10 */
+    int8_t has_plan;     /* prev_count > 0 after the commit: the states below are a plan         11 */
+    int32_t best_cand;   /* fan-out: selected candidate or -1; single solve: -1                  12 */
+    int32_t num_obs;     /* as impc_replan_view.num_obs                                          16 */
+    int32_t ob_idx;      /* as impc_replan_view.ob_idx                                           20 */
+    int32_t status;      /* impc_info.status_val of the instance's QP, else 0                    24 */
+    int32_t iter;        /* impc_info.iter of it, else 0                                         28 */
+    double obj;          /* impc_info.obj_val of it, else 0                                      32 */
+    double score;        /* weighted[inst][best_cand]; 0 unless fan-out with best_cand >= 0      40 */
+    double pri_res, dua_res; /* impc_info.pri_res / dua_res of it, else 0                    48, 56 */
+} impc_replan_record;
+#define IMPC_REPLAN_RECORD_BYTES(plan_steps) (64 + 64 * (int64_t)(plan_steps))
+#ifdef __cplusplus
+static_assert(sizeof(impc_replan_record) == 64, "impc_replan_record is 64 bytes");
+#else
+_Static_assert(sizeof(impc_replan_record) == 64, "impc_replan_record is 64 bytes");
+#endif
+
+/* The records of the last impc_replan_run into `out` (DEVICE, 8-byte aligned, max_inst records of
+ * 64 + 64 plan_steps bytes): rows 0 .. I-1 this object's instances (inst = inst_base + row), rows
+ * I .. max_inst-1 all-zero bytes (the padding of a rank with fewer instances than the largest),
+ * written by the same kernel.  Stream-ordered after the replan on the context stream; no host
+ * synchronisation, no allocation; only reads the replan's state.  IMPC_INVALID_ARGUMENT: a null
+ * object or buffer, plan_steps outside 0..N, max_inst < I, inst_base < 0 or inst_base + I > 2^31,
+ * no impc_replan_run yet. */
+int impc_replan_pack_device(impc_replan rp, int32_t rank, int64_t inst_base, int32_t plan_steps, int64_t max_inst,
+                            void *out);
+/* Every rank's records to every rank: this rank's records packed (as above, rank from the
+ * communicator) straight into its own block of `recv` (DEVICE, world * max_inst records), recv +
+ * rank * max_inst * record bytes, then ONE in-place ncclAllGather on the context stream -- no
+ * staging block.  Ranks may hold different instance counts: max_inst >= every rank's I, the same
+ * on every rank.  Errors as above, and for a communicator created on another context. */
+int impc_replan_gather(impc_replan rp, impc_comm comm, int64_t inst_base, int32_t plan_steps, int64_t max_inst,
+                       void *recv);
 
 /* The vehicle following its plan (mpc_node.cpp:216-224: after a successful makePlan, currPos =
  * getPos(dt), currVel = getVel(dt)): for every instance whose last replan produced a plan

@@ -2563,6 +2563,11 @@ int batch_tlim_device(impc_batch b, double **out) {
     return IMPC_OK;
 }
 double tick_s(impc_ctx ctx) { return ctx->tick_s; }
+int comm_view(impc_comm c, impc_ctx *ctx, int *rank, int *world) {
+    if (!c || !ctx || !rank || !world) return fail(IMPC_INVALID_ARGUMENT, "null communicator");
+    *ctx = c->ctx, *rank = c->rank, *world = c->world;
+    return IMPC_OK;
+}
 int build_rows(impc_mpc_builder bd, int64_t cap, const int64_t *dcount, const int32_t *row_inst, const int64_t *osrc,
                const double *pos, const double *vel, const double *xref, const double *lin, const double *pred_pos,
                const double *pred_size, const double *held_pos, const double *held_size, const double *st_centroid,

@@ -5,6 +5,7 @@
 
 #include <string>
 
+#include "../../include/impc_comm.h"
 #include "../../include/impc_mpc.h"
 #include "../../include/impc_qp.h"
 
@@ -46,6 +47,8 @@ int batch_set_active_device(impc_batch b, const int64_t *d_count);
 int batch_tlim_device(impc_batch b, double **out);
 // seconds per tick of the device clock the time limits run on (hipDeviceAttributeWallClockRate)
 double tick_s(impc_ctx ctx);
+// a communicator's context, rank and world size (comm.hpp)
+int comm_view(impc_comm c, impc_ctx *ctx, int *rank, int *world);
 // The device builder over replan rows (mpc_build.hpp Args: dcount / row_inst / osrc / held arrays;
 // static obstacles per instance, [*][builder's S][3] / [*][S], unread when the builder has none),
 // writing the QP values into a batch's input arrays; asynchronous on `st`.

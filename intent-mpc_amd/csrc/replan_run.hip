@@ -461,6 +461,74 @@ __global__ __launch_bounds__(64) void k_commit(CommitArgs a) {
     }
 }
 
+struct PackArgs {
+    int64_t I, max_inst, inst_base;
+    int32_t N, P, rank;
+    const ShapeDev *sh;
+    const int8_t *branch, *valid, *first_time;
+    const int32_t *prev_count, *best, *num_obs, *ob, *cslot, *slot_row, *shp;
+    const double *weighted, *plan_states;
+    uint64_t *out;  // [max_inst][8 + 8 P] 64-bit words
+};
+
+// What the replan decided per instance (impc_replan_record, include/impc_replan.h): one wavefront
+// per record row, grid-stride over max_inst rows.  The header's eight 64-bit words are composed in
+// registers (every value is uniform over the wavefront) and stored by lanes 0..7; the P stage
+// states follow as 8 P words, lane-strided; rows past I are zero.  Words, not doubles: the copy is
+// bit for bit whatever the value (OSQP_NAN plans included).  The instance's QP is located as
+// k_cand / k_commit locate it.
+__global__ __launch_bounds__(64) void k_pack_records(PackArgs a) {
+    const int lane = threadIdx.x;
+    const int64_t words = 8 + 8 * (int64_t)a.P;
+    for (int64_t row = blockIdx.x; row < a.max_inst; row += gridDim.x) {
+        uint64_t *dst = a.out + row * words;
+        if (row >= a.I) {
+            for (int64_t e = lane; e < words; e += 64) dst[e] = 0;
+            continue;
+        }
+        const int64_t i = row;
+        const int br = a.branch[i], b = a.best[i];
+        int k = -1;
+        int64_t r = -1;
+        double score = 0.0;
+        if (br == IMPC_REPLAN_FANOUT) {
+            if (b >= 0) {
+                const int s = a.cslot[6 * i + b];
+                k = s < 4 ? a.num_obs[i] : a.num_obs[i] + 1;
+                r = a.slot_row[6 * i + s];
+                score = a.weighted[6 * i + b];
+            }
+        } else {
+            k = a.shp[i];
+            r = a.slot_row[6 * i];
+        }
+        impc_info inf{};
+        if (k >= 0 && r >= 0) inf = a.sh[k].info[r];
+        if (lane < 8) {
+            const auto lo_hi = [](int32_t lo, int32_t hi) { return (uint64_t)(uint32_t)lo | (uint64_t)(uint32_t)hi << 32; };
+            uint64_t w;
+            switch (lane) {
+                case 0: w = lo_hi(a.rank, (int32_t)(a.inst_base + i)); break;
+                case 1:
+                    w = lo_hi((int32_t)((uint32_t)(uint8_t)br | (uint32_t)(uint8_t)a.valid[i] << 8 |
+                                        (uint32_t)(uint8_t)(a.first_time[i] != 0) << 16 |
+                                        (uint32_t)(uint8_t)(a.prev_count[i] > 0) << 24),
+                              br == IMPC_REPLAN_FANOUT ? b : -1);
+                    break;
+                case 2: w = lo_hi(a.num_obs[i], a.ob[i]); break;
+                case 3: w = lo_hi((int32_t)inf.status_val, (int32_t)inf.iter); break;
+                case 4: w = (uint64_t)__double_as_longlong(inf.obj_val); break;
+                case 5: w = (uint64_t)__double_as_longlong(score); break;
+                case 6: w = (uint64_t)__double_as_longlong(inf.pri_res); break;
+                default: w = (uint64_t)__double_as_longlong(inf.dua_res); break;
+            }
+            dst[lane] = w;
+        }
+        const uint64_t *src = (const uint64_t *)(a.plan_states + i * (int64_t)a.N * 8);
+        for (int64_t e = lane; e < 8 * (int64_t)a.P; e += 64) dst[8 + e] = src[e];
+    }
+}
+
 // mpcPlanner::getPos / getVel (mpcPlanner.cpp:1257-1290) of every instance with a plan
 __global__ void k_advance(int64_t I, int32_t N, int64_t n, double ts, double t, const int8_t *__restrict__ valid,
                           const double *__restrict__ plan_x, double *__restrict__ pos, double *__restrict__ vel) {
@@ -837,6 +905,7 @@ int impc_replan_view_device(impc_replan rp, impc_replan_view *out) {
     out->first_time = rp->first_time, out->valid = rp->valid, out->branch = rp->branch;
     out->best_cand = rp->best, out->ob_idx = rp->ob, out->cand_type = rp->ctype, out->cand_slot = rp->cslot;
     out->num_obs = rp->num_obs, out->slot_row = rp->slot_row, out->shape = rp->shp;
+    out->weighted = rp->weighted;
     return IMPC_OK;
 }
 
@@ -864,6 +933,56 @@ int impc_replan_shape(impc_replan rp, int32_t obstacles, impc_batch *batch, int6
     if (l) *l = bi.l;
     if (u) *u = bi.u;
     return IMPC_OK;
+}
+
+namespace {
+
+int check_pack(impc_replan rp, int64_t inst_base, int32_t plan_steps, int64_t max_inst, const void *out) {
+    if (!rp) return fail(IMPC_INVALID_ARGUMENT, "replan records: null replan");
+    if (!out) return fail(IMPC_INVALID_ARGUMENT, "replan records: null output buffer");
+    if ((uintptr_t)out % 8) return fail(IMPC_INVALID_ARGUMENT, "replan records: the buffer must be 8-byte aligned");
+    if (plan_steps < 0 || plan_steps > rp->N)
+        return fail(IMPC_INVALID_ARGUMENT, "replan records: plan_steps must be in 0 .. horizon");
+    if (max_inst < rp->I) return fail(IMPC_INVALID_ARGUMENT, "replan records: max_inst is smaller than the instance count");
+    if (inst_base < 0 || inst_base + rp->I > ((int64_t)1 << 31))
+        return fail(IMPC_INVALID_ARGUMENT, "replan records: inst_base >= 0 and inst_base + instances <= 2^31");
+    if (!rp->ran) return fail(IMPC_INVALID_ARGUMENT, "replan records: no impc_replan_run on this object yet");
+    return IMPC_OK;
+}
+
+// k_pack_records on the context stream, after everything the replan queued
+int pack_records(impc_replan rp, int32_t rank, int64_t inst_base, int32_t plan_steps, int64_t max_inst, void *out) {
+    RP_HIP(hipSetDevice(impc_lib::device(rp->ctx)));
+    RP_TRY(impc_lib::order_after_all(rp->ctx));
+    PackArgs pk{rp->I, max_inst, inst_base, rp->N, plan_steps, rank, rp->d_sh, rp->branch, rp->valid, rp->first_time,
+                rp->prev_count, rp->best, rp->num_obs, rp->ob, rp->cslot, rp->slot_row, rp->shp, rp->weighted,
+                rp->plan_states, (uint64_t *)out};
+    hipLaunchKernelGGL(k_pack_records, dim3(grid_for(rp, max_inst, 1)), dim3(64), 0, impc_lib::stream(rp->ctx), pk);
+    RP_HIP(hipGetLastError());
+    return IMPC_OK;
+}
+
+}  // namespace
+
+int impc_replan_pack_device(impc_replan rp, int32_t rank, int64_t inst_base, int32_t plan_steps, int64_t max_inst,
+                            void *out) {
+    RP_TRY(check_pack(rp, inst_base, plan_steps, max_inst, out));
+    return pack_records(rp, rank, inst_base, plan_steps, max_inst, out);
+}
+
+int impc_replan_gather(impc_replan rp, impc_comm comm, int64_t inst_base, int32_t plan_steps, int64_t max_inst,
+                       void *recv) {
+    if (!comm) return fail(IMPC_INVALID_ARGUMENT, "replan records: null communicator");
+    RP_TRY(check_pack(rp, inst_base, plan_steps, max_inst, recv));
+    impc_ctx cctx = nullptr;
+    int rank = 0, world = 1;
+    RP_TRY(impc_lib::comm_view(comm, &cctx, &rank, &world));
+    if (cctx != rp->ctx) return fail(IMPC_INVALID_ARGUMENT, "replan records: the communicator belongs to another context");
+    // in place: this rank's block is packed where the all-gather expects it (send = recv + rank * bytes)
+    const int64_t bytes = max_inst * IMPC_REPLAN_RECORD_BYTES(plan_steps);
+    char *own = (char *)recv + (int64_t)rank * bytes;
+    RP_TRY(pack_records(rp, rank, inst_base, plan_steps, max_inst, own));
+    return impc_comm_allgather(comm, own, recv, bytes, nullptr);
 }
 
 int impc_replan_advance_device(impc_replan rp, double t, double *pos, double *vel) {

@@ -265,6 +265,7 @@ EXPORTED = [
     "impc_batch_update_lin_cost_device", "impc_batch_update_bounds_device", "impc_ctx_pool_stats",
     "impc_replan_create", "impc_replan_destroy", "impc_replan_set_state", "impc_replan_run", "impc_replan_get_stats",
     "impc_replan_view_device", "impc_replan_shape", "impc_replan_advance_device", "impc_batch_follow_plan_device",
+    "impc_replan_pack_device", "impc_replan_gather",  # bound in impc.replan
     "impc_copy_rows_device", "impc_batch_update_matrices", "impc_batch_update_matrices_device",
     "impc_batch_get_persistent",
     "impc_tracks_create", "impc_tracks_destroy", "impc_tracks_push_device", "impc_tracks_reset",
@@ -855,6 +856,11 @@ class Comm:
     def allgather(self, send_ptr, recv_ptr, nbytes, stream=None):
         _check(lib.impc_comm_allgather(self.h, _P(send_ptr), _P(recv_ptr), int(nbytes), _P(stream) if stream else None),
                "impc_comm_allgather")
+
+    def gather_replan_records(self, rp, inst_base, plan_steps, max_inst, recv_ptr):
+        """impc_replan_gather over this communicator: the replan object's per-instance records of
+        its last run to every rank (impc.replan.DeviceReplan.gather_records)."""
+        rp.gather_records(self, inst_base, plan_steps, max_inst, recv_ptr)
 
     def max(self, v):
         d = C.c_double(float(v))

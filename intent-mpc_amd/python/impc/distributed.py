@@ -4,7 +4,8 @@ The path shards by planning instance: every rank owns whole insta
 instance's intent hypotheses stay on one device), so the solve itself needs no collective.  The
 only exchange is the gather of the per-QP result records (instance, hypothesis, objective,
 status, iterations) that the hypothesis selection consumes, plus the max-over-ranks timing of
-bench.py.
+bench.py.  The replan path returns one record per planning instance instead -- what the replan
+decided and the committed plan (impc_replan_gather; pack_replan_records restates its layout).
 
 Transports: the device records move over RCCL/xGMI through the solver library's own
 communicator (impc.Comm, include/impc_comm.h: one ncclAllGather of the packed impc_info
@@ -156,6 +157,58 @@ def replan_records(rank, inst, branch, best_cand, valid, plan_x):
     rec[:, 4] = valid
     rec[:, 5] = px.sum(axis=1)
     rec[:, 6:9] = px[:, 0:3]
+    return rec
+
+
+def pack_replan_records(rank, inst_base, plan_steps, max_inst, view_arrays, shape_infos, weighted):
+    """Host restatement of impc_replan_pack_device (include/impc_replan.h): [max_inst] records of
+    impc.replan.record_dtype(plan_steps), rows past the I instances all zero.  From host arrays:
+    view_arrays = dict(branch, valid, first_time, prev_count, best_cand, num_obs, ob_idx [I],
+    cand_slot, slot_row [I][6], shape [I], and plan_states [I][N][8] or plan_x [I][n] -- the committed
+    plans; what DeviceReplan.results() and plans() return), shape_infos = {k: shape k's impc_info
+    rows} and weighted [I][6] (the selection's scores; None when no instance selected).  Every
+    field is a copy: the instance's QP is its single solve (row slot_row[i][0] of shape[i]), or the
+    selected candidate's (slot s = cand_slot[i][best], row slot_row[i][s] of shape num_obs[i] or,
+    s >= 4, num_obs[i] + 1); a fan-out instance without a selection has none and keeps zeros."""
+    from .replan import FANOUT, record_dtype
+    P = int(plan_steps)
+    va = view_arrays
+    branch = np.asarray(va["branch"])
+    I = branch.shape[0]
+    if max_inst < I:
+        raise ValueError("max_inst is smaller than the instance count")
+    if inst_base < 0 or inst_base + I > 2 ** 31:
+        raise ValueError("inst_base >= 0 and inst_base + instances <= 2^31")
+    states = np.asarray(va["plan_states"] if "plan_states" in va else va["plan_x"], np.float64).reshape(I, -1)
+    if 8 * P > states.shape[1]:
+        raise ValueError("plan_steps exceeds the plans' length")
+    rec = np.zeros(int(max_inst), record_dtype(P))
+    r = rec[:I]
+    r["rank"] = rank
+    r["inst"] = inst_base + np.arange(I)
+    r["branch"] = branch
+    r["valid"] = va["valid"]
+    r["first_time"] = np.asarray(va["first_time"]) != 0
+    r["has_plan"] = np.asarray(va["prev_count"]) > 0
+    fan = branch == FANOUT
+    best = np.where(fan, np.asarray(va["best_cand"]), -1)
+    r["best_cand"] = best
+    r["num_obs"] = va["num_obs"]
+    r["ob_idx"] = va["ob_idx"]
+    r["plan_states"] = states[:, : 8 * P].reshape(I, P, 8)
+    slot, rows, shp, nobs = (np.asarray(va[k]) for k in ("cand_slot", "slot_row", "shape", "num_obs"))
+    for i in range(I):
+        if fan[i]:
+            if best[i] < 0:
+                continue
+            s = int(slot[i, best[i]])
+            k, row = int(nobs[i]) + (1 if s >= 4 else 0), int(rows[i, s])
+            r["score"][i] = weighted[i][best[i]]
+        else:
+            k, row = int(shp[i]), int(rows[i, 0])
+        info = shape_infos[k][row]
+        r["status"][i], r["iter"][i] = info["status_val"], info["iter"]
+        r["obj"][i], r["pri_res"][i], r["dua_res"][i] = info["obj_val"], info["pri_res"], info["dua_res"]
     return rec
 
 

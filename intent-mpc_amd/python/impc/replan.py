@@ -34,7 +34,12 @@ S_st > 0 every QP not on a first plan also carries the instance's S_st static ob
 (obclustering_->getStaticObstacles(), :594; scored by getTrajectoryScore too) and the first plans
 move to shape K + 2.
 
-Everything here beyond impc_replan_run / impc_replan_set_state (input uploads, the per-shape
+What a replan decided leaves the object as one fixed-size record per instance (ReplanRecord +
+plan states, record_dtype): impc_replan_pack_device writes them on the device and
+impc_replan_gather moves every rank's to every rank with one in-place RCCL all-gather
+(DeviceReplan.pack_device / gather_records; host restatement: impc.distributed.pack_replan_records).
+
+Everything here beyond impc_replan_run / impc_replan_set_state and the records (input uploads, the per-shape
 results and assembled values of run()'s return dict) is test plumbing.
 """
 import ctypes as C
@@ -76,7 +81,31 @@ class ReplanStats(C.Structure):
 class ReplanView(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("plan_x", "plan_states", "prev_count", "first_time", "valid", "branch",
                                           "best_cand", "ob_idx", "cand_type", "cand_slot", "num_obs", "slot_row",
-                                          "shape")]
+                                          "shape", "weighted")]
+
+
+class ReplanRecord(C.Structure):
+    """impc_replan_record: the 64-byte header of one instance's record (plan states follow it)."""
+    _fields_ = [("rank", C.c_int32), ("inst", C.c_int32), ("branch", C.c_int8), ("valid", C.c_int8),
+                ("first_time", C.c_int8), ("has_plan", C.c_int8), ("best_cand", C.c_int32), ("num_obs", C.c_int32),
+                ("ob_idx", C.c_int32), ("status", C.c_int32), ("iter", C.c_int32), ("obj", C.c_double),
+                ("score", C.c_double), ("pri_res", C.c_double), ("dua_res", C.c_double)]
+
+
+RECORD_HEADER_BYTES = 64
+_NP_OF = {C.c_int32: np.int32, C.c_int8: np.int8, C.c_double: np.float64}
+
+
+def record_dtype(plan_steps):
+    """numpy structured dtype of one record with plan_steps = P stage states: the header's fields
+    at their C offsets, then plan_states [P][8] float64 at 64; itemsize 64 + 64 P."""
+    P = int(plan_steps)
+    if P < 0:
+        raise ValueError("plan_steps must be >= 0")
+    names = [f for f, _ in ReplanRecord._fields_] + ["plan_states"]
+    formats = [_NP_OF[t] for _, t in ReplanRecord._fields_] + [(np.float64, (P, 8))]
+    offsets = [getattr(ReplanRecord, f).offset for f, _ in ReplanRecord._fields_] + [RECORD_HEADER_BYTES]
+    return np.dtype(dict(names=names, formats=formats, offsets=offsets, itemsize=RECORD_HEADER_BYTES + 64 * P))
 
 
 def _sig(name, *args):
@@ -92,6 +121,8 @@ _sig("impc_replan_run", _P, C.POINTER(ReplanInputs))
 _sig("impc_replan_get_stats", _P, C.POINTER(ReplanStats))
 _sig("impc_replan_view_device", _P, C.POINTER(ReplanView))
 _sig("impc_replan_advance_device", _P, C.c_double, _P, _P)
+_sig("impc_replan_pack_device", _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64, _P)
+_sig("impc_replan_gather", _P, _P, C.c_int64, C.c_int32, C.c_int64, _P)
 _sig("impc_replan_shape", _P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P),
      C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P))
 
@@ -237,6 +268,27 @@ class DeviceReplan:
         instance with a plan (mpc_node.cpp:216-224)."""
         _check(lib.impc_replan_advance_device(self.h, float(t), _P(pos_ptr), _P(vel_ptr)), "impc_replan_advance_device")
 
+    def pack_device(self, rank, inst_base, plan_steps, max_inst, out_ptr):
+        """impc_replan_pack_device: the last replan's records (record_dtype(plan_steps)) into out_ptr
+        (device, max_inst records; rows past I zero), queued after the replan."""
+        _check(lib.impc_replan_pack_device(self.h, int(rank), int(inst_base), int(plan_steps), int(max_inst),
+                                           _P(out_ptr)), "impc_replan_pack_device")
+
+    def gather_records(self, comm, inst_base, plan_steps, max_inst, recv_ptr):
+        """impc_replan_gather: this rank's records packed into its block of recv_ptr (device, world *
+        max_inst records) and one in-place ncclAllGather over `comm` (impc.Comm)."""
+        _check(lib.impc_replan_gather(self.h, comm.h if comm is not None else None, int(inst_base), int(plan_steps),
+                                      int(max_inst), _P(recv_ptr)), "impc_replan_gather")
+
+    def record_arrays(self, out=None):
+        """(view_arrays, shape_infos, weighted) of the last replan on the host, the inputs of
+        impc.distributed.pack_replan_records (out: a results() dict to reuse)."""
+        out = self.results(values=False) if out is None else out
+        plan_x, first_time, prev_count, valid = self.plans()
+        va = {k: out[k] for k in ("branch", "best_cand", "num_obs", "ob_idx", "cand_slot", "slot_row", "shape")}
+        va.update(plan_x=plan_x, first_time=first_time, prev_count=prev_count, valid=valid)
+        return va, {k: s["info"] for k, s in out["shapes"].items()}, out["weighted"]
+
     def stats(self):
         s = ReplanStats()
         _check(lib.impc_replan_get_stats(self.h, C.byref(s)), "impc_replan_get_stats")
@@ -368,8 +420,8 @@ class DeviceReplan:
         return out
 
     def results(self, values=True, profile=False):
-        """Host copies of the last replan's per-instance outputs, state and per-shape results
-        (test / tool inspection after the call)."""
+        """Host copies of the last replan's per-instance outputs (weighted [I][6]: the selection's
+        scores), state and per-shape results (test / tool inspection after the call)."""
         I = self.I
         st = self.stats()
         v = self.view()
@@ -377,7 +429,7 @@ class DeviceReplan:
                    ob_idx=_get(self.ctx, v.ob_idx, I, np.int32), cand_type=_get(self.ctx, v.cand_type, (I, 6), np.int32),
                    cand_slot=_get(self.ctx, v.cand_slot, (I, 6), np.int32), valid=_get(self.ctx, v.valid, I, np.int8),
                    num_obs=_get(self.ctx, v.num_obs, I, np.int32), slot_row=_get(self.ctx, v.slot_row, (I, 6), np.int32),
-                   shape=_get(self.ctx, v.shape, I, np.int32),
+                   shape=_get(self.ctx, v.shape, I, np.int32), weighted=_get(self.ctx, v.weighted, (I, 6), np.float64),
                    issued=bool(st["issued"]), time_limit=st["time_limit"])
         shapes = {}
         for k in range(self.num_shapes):

@@ -18,10 +18,14 @@ is the dormant path at scale).
 
 --gpus N: one process per GPU (started here with torch.distributed.run before anything touches a
 GPU, or under the caller's torchrun); the instances are split in contiguous ranges, every rank
-replans its own (the selection is per instance: no exchange inside a replan), a barrier and the
-max over ranks bound each replan's time, and the last replan's per-instance records
-(impc.distributed.replan_records) reach every rank.  The rate is all ranks' instances over that
-time.  The same loop at small I is checked replan by replan against the restatements in
+replans its own (the selection is per instance: no exchange inside a replan) and, after every replan,
+each instance's record (impc_replan_record: what the replan decided and --plan-steps stage states of
+the committed plan) reaches every rank: impc_replan_gather packs them on the device and moves them
+with one in-place ncclAllGather on the context stream, inside the replan's timed span (on one GPU a
+communicator of one rank runs the same path).  A barrier and the max over ranks bound each
+replan's time.  With IMPC_RANK_DEVICE putting every rank on one device (a rehearsal; RCCL refuses
+that) the records are packed on the device, copied to the host and gathered over gloo.  The rate is
+all ranks' instances over that time.  The same loop at small I is checked replan by replan against the restatements in
 tests/test_live_loop.py; the rank split in tests/test_distributed.py.
 
 --detector [--range 30.0] [--hist 100]: the detector in the loop instead of baked predictions
@@ -153,6 +157,8 @@ def main():
     ap.add_argument("--mixed-k", action="store_true", help="per-instance obstacle counts K_i in 0..K per replan")
     ap.add_argument("--statics", type=int, default=0, help="static obstacles per instance (num_static)")
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--plan-steps", type=int, default=None,
+                    help="stage states of the plan in every gathered record (0..horizon; default: the horizon)")
     ap.add_argument("--detector", action="store_true", help="gate + predictor + replan per tick (DeviceTick)")
     ap.add_argument("--range", type=float, default=30.0, help="--detector: sensor range (color_distance)")
     ap.add_argument("--hist", type=int, default=100, help="--detector: history entries per track (history_size)")
@@ -167,7 +173,7 @@ def main():
     import impc  # noqa: E402  (after a possible relaunch: nothing touched the GPU before it)
     from impc import distributed as D  # noqa: E402
     from impc import scenarios  # noqa: E402
-    from impc.replan import DeviceReplan  # noqa: E402
+    from impc.replan import DeviceReplan, record_dtype  # noqa: E402
     rank, local_rank, world = D.env()
     if world != a.gpus:
         sys.exit(f"live_loop.py: --gpus {a.gpus} but WORLD_SIZE={world}")
@@ -207,28 +213,50 @@ def main():
     st_d = [Dv(ctx, c(x)) for x in static] if static is not None else []
     st_ptr = dict(zip(("st_centroid", "st_size", "st_yaw"), (d.ptr for d in st_d)))
     step_pred, step_cur = pred_d.nbytes // R, cur_d.nbytes // R
-    walls, stats = [], []
+    # every replan's per-instance records to every rank (impc_replan_gather: pack + ONE in-place
+    # ncclAllGather on the context stream).  RCCL refuses several ranks on one device, so the
+    # IMPC_RANK_DEVICE rehearsal packs on the device, copies the block to the host and gathers over gloo.
+    counts = [int(bounds[k + 1] - bounds[k]) for k in range(world)]
+    max_inst = max(counts)
+    P = N if a.plan_steps is None else a.plan_steps
+    rec_dt = record_dtype(P)
+    rehearsal = world > 1 and "IMPC_RANK_DEVICE" in os.environ
+    comm = None if rehearsal else D.make_comm(dist, ctx)
+    recv_d = Dv(ctx, ((1 if rehearsal else world) * max_inst * rec_dt.itemsize,), np.uint8)
+    walls, stats, gathered, allrec = [], [], [], None
     for r in range(R):
         ctx.synchronize()
         if dist is not None:
             dist.barrier()
         t = time.perf_counter()
         paths.xref_device(pos_d.ptr, xref_d.ptr)
+        ctx.timer_mark()
         rp.run_device(pos_d.ptr, vel_d.ptr, xref_d.ptr, cur_d.ptr + r * step_cur, pred_d.ptr + r * step_pred,
                       psize_d.ptr, prob_d.ptr, num_pred=None if np_d is None else np_d.ptr + r * 4 * I, **st_ptr)
+        ctx.timer_mark()
         rp.advance_device(pd["ts"], pos_d.ptr, vel_d.ptr)
+        if rehearsal:
+            rp.pack_device(rank, lo, P, max_inst, recv_d.ptr)
+            block = recv_d.get()[: I * rec_dt.itemsize].reshape(I, rec_dt.itemsize)  # the one D2H of the rehearsal
+            allrec = np.frombuffer(D.gather_costs(dist, block, counts).tobytes(), rec_dt)
+        else:
+            ctx.timer_mark()
+            rp.gather_records(comm, lo, P, max_inst, recv_d.ptr)
+            ctx.timer_mark()
         ctx.synchronize()
         if dist is not None:
             dist.barrier()
         walls.append(D.max_over_ranks(dist, time.perf_counter() - t))
+        if not rehearsal:  # outside the timed replan: what this rank now holds
+            allrec = D.unpad(np.frombuffer(recv_d.get().tobytes(), rec_dt), counts)
+        gathered.append(int(np.count_nonzero(allrec["inst"] == np.arange(allrec.shape[0]))))
         st = rp.stats()
         stats.append((st["fanout"], st["single_first"], st["single_current"]))
+    ms = ctx.timer_read(max_pairs=2 * R).reshape(R, -1)  # per replan: the replan, then (device path) the gather
+    replan_ms, gather_ms = ms[:, 0].tolist(), [] if rehearsal else ms[:, 1].tolist()
     last = rp.results(values=False)
     its = np.concatenate([s["info"]["iter"] for s in last["shapes"].values()])
     sts = np.concatenate([s["info"]["status_val"] for s in last["shapes"].values()])
-    plan_x, _, _, valid = rp.plans()
-    rec = D.replan_records(rank, np.arange(lo, hi), last["branch"], last["best_cand"], valid, plan_x)
-    allrec = D.gather_costs(dist, rec, [int(bounds[k + 1] - bounds[k]) for k in range(world)])
     st_all = D.gather_costs(dist, np.array([stats[-1]], np.float64), [1] * world)
     w = np.array(walls)
     fan = w[1:]  # replans 1..R-1: every instance past its first plan
@@ -247,10 +275,18 @@ def main():
                                   "status_counts": {str(int(k)): int(v) for k, v in zip(*np.unique(sts, return_counts=True))},
                                   "shapes": {str(k): int(s["x"].shape[0]) for k, s in last["shapes"].items()}},
             "qp_solves_per_s_rank0": float(n_qps / np.median(fan)),
-            "valid_plans": int(allrec[:, 4].sum()), "records_gathered": int(allrec.shape[0]),
+            "valid_plans": int(allrec["valid"].sum()), "records_gathered": gathered[-1],
+            "records": {"plan_steps": P, "bytes_per_record": rec_dt.itemsize,
+                        "bytes_per_rank": max_inst * rec_dt.itemsize,
+                        "transport": "gloo (one-device rehearsal)" if rehearsal else "rccl",
+                        "gathered_per_replan": gathered, "gather_ms": gather_ms,
+                        "gather_ms_median": float(np.median(gather_ms[1:])) if len(gather_ms) > 1 else None,
+                        "replan_ms_median": float(np.median(replan_ms[1:])) if R > 1 else None},
             "ref_start_idx_mean": float(paths.last_idx().mean()), "gen_s": gen_s,
             "build_id": impc.lib.impc_build_id().decode()}), flush=True)
-    for d in (pos_d, vel_d, xref_d, psize_d, prob_d, pred_d, cur_d) + ((np_d,) if np_d is not None else ()) + tuple(st_d):
+    if comm is not None:
+        comm.close()
+    for d in (pos_d, vel_d, xref_d, psize_d, prob_d, pred_d, cur_d, recv_d) + ((np_d,) if np_d is not None else ()) + tuple(st_d):
         d.free()
     paths.close()
     rp.close()
