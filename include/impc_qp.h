@@ -277,6 +277,13 @@ typedef struct {
     int64_t team_lanes, var_slots, row_slots;
 } impc_batch_stats;
 int impc_batch_get_stats(impc_batch b, impc_batch_stats *out);
+/* Occupancy of the structured kernel (either pointer may be NULL): the resident teams (QPs) per CU
+ * of the kernel instance that ran the batch's last structured launch -- 0 before the first one;
+ * the team shape runs two per CU, or three in a launch of more than 32 QPs per CU of default-horizon
+ * batches that each hold that many and fit a third of the CU's LDS (IMPC_TEAMS_PER_CU=2|3 in the
+ * environment, read when a batch is created and when a launch is issued, forces either) --
+ * and the dynamic LDS bytes one QP of the batch takes (0: no structured kernel for the pattern). */
+int impc_batch_get_occupancy(impc_batch b, int64_t *teams_per_cu, int64_t *lds_bytes);
 
 /* Kernel timing with HIP events recorded on the solve stream around k_setup, k_solve and the
  * output transposes (profiling on: events are recorded by every subsequent setup/solve). */

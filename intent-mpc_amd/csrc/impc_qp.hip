@@ -64,8 +64,10 @@ int fail(int code, const std::string &msg) {
 constexpr int kBlock = 64;  // generic path: one wavefront per workgroup, one QP per lane
 constexpr int kTile = 64;   // transpose tile edge
 // Structured path team shapes, keyed by the variable slots per lane VS:
-//   VS = 1  team shape: one QP per 256-lane workgroup (one variable per lane), two teams per CU
-//           (n <= 256: the reference's default horizon N = 20)
+//   VS = 1  team shape: one QP per 256-lane workgroup (one variable per lane), two teams per CU,
+//           or three (a second instance of the kernel, 168 VGPRs) for a launch of more than
+//           kDenseMinPerCu QPs per CU whose batches' LDS fits a third of the CU (n <= 256: the
+//           reference's default horizon N = 20)
 //   VS = 3  long shape: 256 lanes, three variables per lane, one team per CU (n <= 768)
 //   VS = 4  wavefront shape (built only with IMPC_WAVEFRONT=1: measured slower):
 //           one QP per 64-lane wavefront (four variables and up to six general rows per lane, D / E
@@ -82,7 +84,14 @@ struct Shape {
     // the two-tier products instances (mpc_wave.hpp WaveLds): general-row slot counts that have them
     static constexpr int TIER_GMAX = VS == kWaveVSFront ? 6 : VS == kWaveVS ? 3 : 1;
     static constexpr int PER_CU = 4 * WPS / (NL / 64);        // resident QPs per CU by waves
+    // the denser instance (waves per SIMD, = QPs per CU of a 256-lane team) and the general-row
+    // slot counts that have it; WPS where the shape has none
+    static constexpr int WPS_HI = VS == kWaveVS ? 3 : WPS;
+    // (a pattern with three general-row slots, mg > 512, takes more LDS than a third of the CU)
+    static constexpr int HI_GMAX = VS == kWaveVS ? 2 : 0;
+    static constexpr int PER_CU_HI = 4 * WPS_HI / (NL / 64);
 };
+constexpr size_t kCuLds = 160 * 1024 - 1024;  // dynamic LDS the resident teams of a CU share
 
 // ------------------------------------------------------------------ layout transposes
 // dst[e * S + b] = src[b * len + e]; 64x64 tile through LDS so both sides are coalesced.
@@ -650,6 +659,8 @@ struct impc_batch_s {
     bool tier = false;  // two-tier products layout (grouped-kernel instances only)
     int gs = 0;  // general-row slots per lane of the structured kernel
     int vs = 1;  // variable slots per lane (kWaveVS, or kWaveVSLong for long horizons)
+    int last_teams = 0;  // resident teams per CU of the batch's last structured launch (0: none yet)
+    bool dense = false;  // LDS layout chosen for the denser instance (choose_shape)
     void *d_tables = nullptr;
     double *d_scal = nullptr;
     unsigned *d_counter = nullptr;
@@ -939,11 +950,17 @@ int ensure_lds_attr(K kernel, size_t lds) {
     return IMPC_OK;
 }
 
-// resident workgroups per CU: the waves-per-SIMD budget of the shape, and LDS
-template <int VS>
-int64_t resident_groups(int num_cu, size_t lds, int64_t work) {
-    const int per_cu = std::max<int>(1, std::min<int>(Shape<VS>::PER_CU, (int)((160 * 1024 - 1024) / lds)));
+// resident workgroups per CU: the waves-per-SIMD budget of the launched instance (teams), and LDS
+int64_t resident_groups(int num_cu, int teams, size_t lds, int64_t work) {
+    const int per_cu = std::max<int>(1, std::min<int>(teams, (int)(kCuLds / lds)));
     return std::min<int64_t>(work, (int64_t)num_cu * per_cu);
+}
+
+// IMPC_TEAMS_PER_CU=2|3 in the environment forces the team shape's two- or three-per-CU instance
+// (A/B and tests; read when a batch's layout is chosen and when a launch is issued); 0: not set
+int teams_env() {
+    const char *e = std::getenv("IMPC_TEAMS_PER_CU");
+    return e && (e[0] == '2' || e[0] == '3') && !e[1] ? e[0] - '0' : 0;
 }
 
 // the compile-time horizon instance that takes the batch: its W when the shape has one for it
@@ -1091,29 +1108,76 @@ int structured_solve(impc_batch b, hipStream_t st) {
     return impc_batch_solve_group(&b, 1, st);
 }
 
-template <int VS, int GS, int WF, bool TIER>
-int launch_group_w(impc_ctx ctx, hipStream_t st, const GroupEntry *entries, int count, int64_t total, size_t lds,
-                   unsigned *counter, const uint32_t *ord, int devcnt) {
+// The instances built at the denser occupancy: the default horizon's two-tier one (the bench's),
+// whose iteration loop at 168 VGPRs reloads 7 values from scratch, none inside the sweeps.  The
+// one-tier and runtime-horizon instances compile to 9-21 reloads per iteration at three waves per
+// SIMD (the runtime-horizon one-tier instance with two inside a sweep), above the 8 of the plain
+// launch-bound change, and stay at the plain occupancy (profiles/r08/isa_loops_dense_not_built.txt).
+constexpr bool dense_instance(int vs, int gs, int wf, bool tier) {
+    return vs == kWaveVS && gs <= Shape<kWaveVS>::HI_GMAX && tier && wf != 0 &&
+           wf == impc::WaveLds<256, kWaveVS, 2>::WSPEC;
+}
+
+template <int VS, int GS, int WPS, int WF, bool TIER>
+int launch_group_wps(impc_ctx ctx, hipStream_t st, const GroupEntry *entries, int count, int64_t total, size_t lds,
+                     unsigned *counter, const uint32_t *ord, int devcnt) {
     using S = Shape<VS>;
-    if (int rc = ensure_lds_attr(k_mpc_wave_group<S::NL, VS, GS, S::WPS, WF, TIER>, lds)) return rc;
-    const int64_t groups = resident_groups<VS>(ctx->num_cu, lds, total);
-    hipLaunchKernelGGL((k_mpc_wave_group<S::NL, VS, GS, S::WPS, WF, TIER>), dim3((unsigned)groups), dim3(S::NL), lds,
-                       st, entries, count, total, counter, ord, devcnt);
+    if (int rc = ensure_lds_attr(k_mpc_wave_group<S::NL, VS, GS, WPS, WF, TIER>, lds)) return rc;
+    const int64_t groups = resident_groups(ctx->num_cu, 4 * WPS / (S::NL / 64), lds, total);
+    hipLaunchKernelGGL((k_mpc_wave_group<S::NL, VS, GS, WPS, WF, TIER>), dim3((unsigned)groups), dim3(S::NL), lds, st,
+                       entries, count, total, counter, ord, devcnt);
     HIP_OK(hipGetLastError());
     return IMPC_OK;
+}
+// teams: the resident teams per CU of the instance to launch (launch_teams)
+template <int VS, int GS, int WF, bool TIER>
+int launch_group_w(impc_ctx ctx, hipStream_t st, const GroupEntry *entries, int count, int64_t total, size_t lds,
+                   unsigned *counter, const uint32_t *ord, int devcnt, int teams) {
+    using S = Shape<VS>;
+    if constexpr (dense_instance(VS, GS, WF, TIER))
+        if (teams == S::PER_CU_HI)
+            return launch_group_wps<VS, GS, S::WPS_HI, WF, TIER>(ctx, st, entries, count, total, lds, counter, ord,
+                                                                  devcnt);
+    return launch_group_wps<VS, GS, S::WPS, WF, TIER>(ctx, st, entries, count, total, lds, counter, ord, devcnt);
 }
 // spec: the compile-time horizon every batch of the launch shares (spec_w), or 0
 template <int VS, int GS, bool TIER = false>
 int launch_group(impc_ctx ctx, hipStream_t st, const GroupEntry *entries, int count, int64_t total, size_t lds,
-                 unsigned *counter, int spec, const uint32_t *ord, int devcnt) {
+                 unsigned *counter, int spec, const uint32_t *ord, int devcnt, int teams) {
     using LD = impc::WaveLds<Shape<VS>::NL, VS, GS>;
     constexpr int WS = LD::WSPEC, WS2 = LD::WSPEC2;
     if (spec && spec == WS)
-        return launch_group_w<VS, GS, WS, TIER>(ctx, st, entries, count, total, lds, counter, ord, devcnt);
+        return launch_group_w<VS, GS, WS, TIER>(ctx, st, entries, count, total, lds, counter, ord, devcnt, teams);
     if constexpr (WS2 != 0)
         if (spec == WS2)
-            return launch_group_w<VS, GS, WS2, TIER>(ctx, st, entries, count, total, lds, counter, ord, devcnt);
-    return launch_group_w<VS, GS, 0, TIER>(ctx, st, entries, count, total, lds, counter, ord, devcnt);
+            return launch_group_w<VS, GS, WS2, TIER>(ctx, st, entries, count, total, lds, counter, ord, devcnt, teams);
+    return launch_group_w<VS, GS, 0, TIER>(ctx, st, entries, count, total, lds, counter, ord, devcnt, teams);
+}
+
+// QPs per CU from which a launch (or, for its LDS layout, a batch) takes the denser instance.  A
+// third team per CU hides the others' dependent chains (config 3: -9 % per launch) but lengthens
+// each QP's own latency by about a third, and a launch is never shorter than its longest QP: a
+// 4,000-iteration QP takes 12 ms at two teams per CU and 15 ms at three, while 512 average QPs take
+// 1.6 ms of a two-per-CU launch.  Below about 20 QPs per CU the longer tail costs more than the
+// denser bulk saves (config 4's buckets of 350-1,300 QPs, one launch each: +19-23 %; 3,072
+// candidates: +17 %); from 32 on the bulk's gain is at least twice the tail's loss.
+constexpr int64_t kDenseMinPerCu = 32;
+
+// Resident teams per CU of a grouped launch of shape (vs, gs, tier) and compile-time horizon spec:
+// the denser instance when it is built for them (dense_instance), every batch was laid out for it
+// (dense: choose_shape, a batch of more than kDenseMinPerCu QPs per CU -- config 4's class of
+// K = 13..18 buckets of 350-1,300 QPs, 9k together, ran slower at three per CU), every batch's LDS
+// fits its share of the CU (lds: the launch's largest) and the launch has more than kDenseMinPerCu
+// QPs per CU; a smaller launch (one planner's candidates) keeps the plain instance.  IMPC_TEAMS_PER_CU forces
+// either.
+int launch_teams(int vs, int gs, bool tier, int spec, bool dense, size_t lds, int64_t total, int num_cu) {
+    const int lo = vs == kWaveVS ? Shape<kWaveVS>::PER_CU
+                                 : vs == kWaveVSLong ? Shape<kWaveVSLong>::PER_CU : Shape<kWaveVSFront>::PER_CU;
+    const int hi = Shape<kWaveVS>::PER_CU_HI;
+    if (!dense || !dense_instance(vs, gs, spec, tier) || lds > kCuLds / (size_t)hi) return lo;
+    const int forced = teams_env();
+    if (forced) return forced == hi ? hi : lo;
+    return total > kDenseMinPerCu * num_cu ? hi : lo;
 }
 
 // dynamic LDS bytes of the structured kernel for a shape (team VS, GS) and pattern (CG, n); 0 if
@@ -1145,6 +1209,7 @@ bool wavefront_shape_on() {
 // Shape selection: (when built) the wavefront shape if the pattern fits it with four QPs per CU,
 // else the team shape (n <= 256), else the long shape.  Sets b->vs, b->gs, b->tier and the tables' layout
 // fields; false if no structured shape takes the pattern.
+constexpr size_t kTierMargin = 8192;
 bool choose_shape(impc_batch b) {
     const impc::MpcStructure &s = *b->ms;
     impc::WaveTables &t = b->wt;
@@ -1160,12 +1225,17 @@ bool choose_shape(impc_batch b) {
         if (s.n > nl * vs) return false;
         const int g = std::max(2, (s.mg + nl - 1) / nl);  // general-row slots per lane
         if (g > gmax) return false;
-        const size_t budget = (160 * 1024 - 1024) / (size_t)per_cu;
+        const size_t budget = kCuLds / (size_t)per_cu;
         // products layout (mpc_wave.hpp WaveLds): one tier unless it would cost the shape a resident
         // team per CU, then the heavy columns' overflow in a second tier
         t.HS = 0;
         t.T1r = impc::WaveLds<256, kWaveVS, 2>::cg4(s.CG);
-        if (g <= tier_gmax && wave_lds_bytes(vs, g, t) > budget) {
+        // (The team shape at two per CU goes to two tiers kTierMargin below the budget: a pattern
+        // that close to it gathers CG4 >= 16 rows per column in one tier, and with K = 13 / 14 of
+        // N = 20 in one tier config 4 ran 1.2 % slower, profiles/r08/kernel_ab.txt.)
+        size_t one = wave_lds_bytes(vs, g, t);
+        if (vs == kWaveVS && per_cu == Shape<kWaveVS>::PER_CU && one) one += kTierMargin;
+        if (g <= tier_gmax && one > budget) {
             t.HS = s.HS;
             t.T1r = impc::kProdTier1;
         }
@@ -1188,6 +1258,18 @@ bool choose_shape(impc_batch b) {
     using T1 = Shape<kWaveVS>;
     using L = Shape<kWaveVSLong>;
     if (wavefront_shape_on() && fit(kWaveVSFront, F::NL, F::GMAX, F::TIER_GMAX, F::PER_CU, true)) return true;
+    // The team shape's layout for three teams per CU (the per-team budget of the denser instance:
+    // the two-tier products where one tier would not fit it) when the batch alone has the QPs that
+    // make the denser instance pay (launch_teams) or IMPC_TEAMS_PER_CU=3 asks; a smaller batch
+    // keeps the two-per-CU layout -- and with it its kernel class, so the buckets of a mixed group
+    // do not split into more launches -- and stays at two per CU (launch_teams).
+    const int forced = teams_env();
+    if ((forced ? forced == T1::PER_CU_HI : b->B > kDenseMinPerCu * b->ctx->num_cu) &&
+        s.W == impc::WaveLds<256, kWaveVS, 2>::WSPEC &&
+        fit(kWaveVS, T1::NL, T1::HI_GMAX, T1::TIER_GMAX, T1::PER_CU_HI, true) && b->tier) {
+        b->dense = true;
+        return true;
+    }
     if (fit(kWaveVS, T1::NL, T1::GMAX, T1::TIER_GMAX, T1::PER_CU, false)) return true;
     return fit(kWaveVSLong, L::NL, L::GMAX, L::TIER_GMAX, L::PER_CU, false);
 }
@@ -1871,6 +1953,7 @@ int impc_batch_solve_group(impc_batch *bs, int count, void *stream) {
         int spec;  // the launch's compile-time horizon (-1: no batch yet; 0: runtime W)
         unsigned *counter;
         bool devcnt;  // some batch's active count is in device memory
+        bool dense = true;  // every batch laid out for the denser instance
     };
     std::vector<Launch> launches;
     HIP_OK(hipSetDevice(ctx->device));
@@ -1885,6 +1968,7 @@ int impc_batch_solve_group(impc_batch *bs, int count, void *stream) {
         Launch &L = launches.back();
         L.count++;
         L.lds = std::max(L.lds, wave_lds_bytes(b->vs, b->gs, b->wt));
+        L.dense = L.dense && b->dense;
         L.spec = L.spec < 0 ? spec_w(b) : (L.spec == spec_w(b) ? L.spec : 0);
         GroupEntry &e = entries[(size_t)p];
         e.T = b->wt;
@@ -1898,7 +1982,7 @@ int impc_batch_solve_group(impc_batch *bs, int count, void *stream) {
         b->ev_setup = false;
     }
     for (const Launch &L : launches)
-        if (L.lds > 160 * 1024 - 1024) return fail(IMPC_UNSUPPORTED, "grouped batches exceed the LDS of a CU");
+        if (L.lds > kCuLds) return fail(IMPC_UNSUPPORTED, "grouped batches exceed the LDS of a CU");
     // the entry table: a cached device copy of these very entries (repeated solves of one group,
     // or of the few groups a pipeline alternates between), else a fresh table -- uploaded on the
     // launch stream; replacing a cached table that a launch in flight may read waits for every
@@ -1943,11 +2027,13 @@ int impc_batch_solve_group(impc_batch *bs, int count, void *stream) {
         }
         const uint32_t *ord = nullptr;
         IMPC_TRY(queue_order(lb.data(), lf.data(), L.count, L.total, st, &ord));
+        const int teams = launch_teams(L.vs, L.gs, L.tier, L.spec, L.dense, L.lds, L.total, ctx->num_cu);
         const int rc = with_shape(L.vs, L.gs, L.tier, [&](auto vs, auto gs, auto tr) {
             return launch_group<decltype(vs)::value, decltype(gs)::value, decltype(tr)::value>(
-                ctx, st, E, L.count, L.total, L.lds, L.counter, L.spec, ord, L.devcnt ? 1 : 0);
+                ctx, st, E, L.count, L.total, L.lds, L.counter, L.spec, ord, L.devcnt ? 1 : 0, teams);
         });
         if (rc) return rc;
+        for (impc_batch b : lb) b->last_teams = teams;
     }
     IMPC_TRY(ctx_note_launch(ctx, st));
     for (int k = 0; k < count; k++) structured_solved(bs[k]);
@@ -2219,6 +2305,13 @@ int impc_batch_get_stats(impc_batch b, impc_batch_stats *out) {
         out->var_slots = b->vs;
         out->row_slots = b->gs;
     }
+    return IMPC_OK;
+}
+
+int impc_batch_get_occupancy(impc_batch b, int64_t *teams_per_cu, int64_t *lds_bytes) {
+    if (!b) return fail(IMPC_INVALID_ARGUMENT, "null batch");
+    if (teams_per_cu) *teams_per_cu = b->last_teams;
+    if (lds_bytes) *lds_bytes = b->structured_ok ? (int64_t)wave_lds_bytes(b->vs, b->gs, b->wt) : 0;
     return IMPC_OK;
 }
 

@@ -1,5 +1,5 @@
 // mpc_wave.hpp -- the structured kernel's body: one mpcPlanner QP per team of NL = 256 lanes
-// (4 wavefronts, one workgroup), all per-QP state on chip, 2 teams per CU.
+// (4 wavefronts, one workgroup), all per-QP state on chip, 2 or 3 teams per CU.
 //
 // Why: the ADMM of OSQP 0.6.2 (reference osqp.h:78, osqp_solve) runs hundreds to thousands of
 // iterations per QP; each needs one solve with M = P + sigma I + A' R A plus two SpMVs.  Streaming
@@ -10,7 +10,8 @@
 // iterations do not stall the ones that need 200.
 //
 // Shapes (template VS = variables per lane): VS = 1 (n <= 256, the reference's default horizon
-// N = 20) at 2 waves per SIMD; VS = 3 (n <= 768, N <= 59) at 1 wave per SIMD.  GS = 2..4
+// N = 20) at 2 waves per SIMD, or 3 in a launch with the QPs to fill a third team per CU whose
+// batches' LDS fits it (the host's launch_teams); VS = 3 (n <= 768, N <= 59) at 1 wave per SIMD.  GS = 2..4
 // general-row slots per lane.  WF = the shape's default stage count (19 / 39) as a compile-time
 // constant, or 0 for any horizon.  TIER = the two-tier products layout (WaveLds) for obstacle-heavy
 // patterns whose one-tier products would cost the CU its second team.
@@ -20,8 +21,8 @@
 //       (A value, z, y, l, u, type), row v'%13 of Ainv_k (13) and an 8-wide coupling row
 //   general-row slot s    <-> g = NL s + L    (GS slots): 4 A values + columns, z, y, l, u, type
 //   LDS (WaveLds): F_k (the 8x8 stage-coupling blocks), exchange vectors r / t / e / x~, team
-//       reduction scratch, the int16 entry -> product-slot table, D / E and the check deltas
-//       (VS = 1), the products buffer (column-slot layout)
+//       reduction scratch, the int16 entry -> product-slot table, D / E (VS = 1), the products
+//       buffer (column-slot layout); the check deltas of VS = 1 take dead LDS (WaveLds::DLT_OFF)
 //
 // Linear solve (block LDL^T of the stage-tridiagonal M, with Ahat_k the Schur complements):
 //   G_k = Bbar_k Ahat_k^{-1} (8 x 13), F_k = G_k[:, :8]
@@ -237,14 +238,22 @@ struct WaveLds {
     static constexpr int RED_OFF = X_OFF + NP;              // team reduction scratch [kRedLen]
     static constexpr int JUNK_OFF = RED_OFF + kRedLen;      // per-lane discard slots [NL]
     static constexpr int GSLOT_OFF = JUNK_OFF + NL;         // int16 [4 NL GS]: general entry -> product slot
-    // One-variable-per-lane shape: the Ruiz scaling vectors D, E and the ADMM deltas of the
-    // termination checks live here (the long-horizon shape keeps them in HBM / registers: its LDS
-    // is full).  Layout of each: [var slots NMAX][box rows NMAX][general slots NL GS].
+    // One-variable-per-lane shape: the Ruiz scaling vectors D, E live here (the long-horizon shape
+    // keeps them in HBM / registers: its LDS is full).  Layout: [var slots NMAX][box rows NMAX]
+    // [general slots NL GS].
     static constexpr bool ONCHIP = VS == 1;
     static constexpr int VEC_N = 2 * NMAX + NL * GS;
     static constexpr int SCL_OFF = GSLOT_OFF + NL * GS;           // D, E (scaling)
-    static constexpr int DLT_OFF = SCL_OFF + (ONCHIP ? VEC_N : 0);  // dx, dy (check iterations)
-    static constexpr int P_OFF = DLT_OFF + (ONCHIP ? VEC_N : 0);  // products, column-slot layout (size below)
+    // The ADMM deltas dx, dy of that shape (written by the update phase of a check iteration, read
+    // only by the check that follows it, each lane its own) take LDS that is dead between an
+    // iteration's S5 and the next rhs gather, at compile-time offsets: dx[v] in the per-lane
+    // discard slots, dy of the box rows in R[0 .. NL), dy of general-row slots 0 and 1 in
+    // T[0 .. NL) and E[0 .. NL).  The exchange vectors' tails stay out (S3 of the default horizon's
+    // last stage reads R[NMAX .. NMAX + 4) and needs the zeros there).  General-row slots 2 and up
+    // (mg > 512) keep a region of their own, DLT_OFF.
+    static constexpr int DLT_OFF = SCL_OFF + (ONCHIP ? VEC_N : 0);
+    static constexpr int DLT_N = ONCHIP && GS > 2 ? NL * (GS - 2) : 0;
+    static constexpr int P_OFF = DLT_OFF + DLT_N;  // products, column-slot layout (size below)
     static constexpr int CGM = 24;                          // max general entries per column
     // products region: entry t < T1r of column v at t * stride(n) + v (stride = n rounded up to
     // 64, plus a pad), so a column's gather is independent, conflict-free reads.  When that one
@@ -389,12 +398,16 @@ struct WaveQP {
     IMPC_WF double rhoig_(int s) const { return R.inv(gt[s]); }
 
     // ADMM deltas of the last iteration (termination checks only): LDS or registers
-    IMPC_WF double &dxv(int s) { if constexpr (LD::ONCHIP) return lds[LD::DLT_OFF + NL * s + L]; else return dxv_[s]; }
-    IMPC_WF double &dyb(int s) {
-        if constexpr (LD::ONCHIP) return lds[LD::DLT_OFF + LD::NMAX + NL * s + L]; else return dyb_[s];
+    // (LDS of the one-variable-per-lane shape: WaveLds::DLT_OFF's comment)
+    IMPC_WF double &dxv(int s) {
+        if constexpr (LD::ONCHIP) return lds[LD::JUNK_OFF + NL * s + L]; else return dxv_[s];
     }
+    IMPC_WF double &dyb(int s) { if constexpr (LD::ONCHIP) return lds[LD::R_OFF + NL * s + L]; else return dyb_[s]; }
     IMPC_WF double &dyg(int s) {
-        if constexpr (LD::ONCHIP) return lds[LD::DLT_OFF + 2 * LD::NMAX + NL * s + L]; else return dyg_[s];
+        if constexpr (LD::ONCHIP)
+            return lds[(s == 0 ? LD::T_OFF : s == 1 ? LD::E_OFF : LD::DLT_OFF + NL * (s - 2)) + L];
+        else
+            return dyg_[s];
     }
     // scaling vectors D, E (set by scale(), read at warm start, checks and unscaling): layout
     // [D n][E box n][E general mg], in LDS or in the per-QP HBM scratch
@@ -510,10 +523,12 @@ struct WaveQP {
                 ug[s] = dmin(dmax(io.u[bm + row], -kInf), kInf);
             }
         }
-        if constexpr (LD::ONCHIP) {  // deltas read by a check before any ADMM step (max_iter = 0)
-            _Pragma("unroll") for (int s = 0; s < VS; s++) dxv(s) = dyb(s) = 0.0;
-            _Pragma("unroll") for (int s = 0; s < GS; s++) dyg(s) = 0.0;
-        }
+        // deltas read by a check before any ADMM step: zero.  Those in the exchange vectors are
+        // zeroed with them at the end of factorize(), after the setup's last use of that LDS as
+        // scratch, and dx after it in solve() (the discard slots still hold the wavefronts'
+        // placement here); the region of slots 2 and up here
+        if constexpr (LD::ONCHIP)
+            _Pragma("unroll") for (int s = 2; s < GS; s++) dyg(s) = 0.0;
     }
 
     // Per-workgroup tables (once per launch): the product slot of every general-row entry
@@ -1950,6 +1965,8 @@ struct WaveQP {
             wv.sync();
             return;
         }
+        if constexpr (LD::ONCHIP)  // dx of a check before any ADMM step (load())
+            _Pragma("unroll") for (int s = 0; s < VS; s++) dxv(s) = 0.0;
         // iterates: zero, then osqp_warm_start (x <- Dinv x, y <- c Einv y, z <- A x)
         if (ps && io.resume && !io.has_ws && st.warm_start) {  // OSQP keeps its iterates between solves
             const double *it = ps + kPersistHdr;
@@ -2032,9 +2049,23 @@ struct WaveQP {
                 // through the loop's one exit -- the pass bound drops to 0, the status register
                 // carries the mark -- so no second exit edge (and its live values) burdens the
                 // register allocation of the passes (round 6: 217.5 -> 213.9 ms per config-3 launch)
+                // A rho update on the solve's last iteration: no pass follows, and the post-loop
+                // checks read that iteration's deltas, which share the exchange vectors with the
+                // factorisation's scratch -- each lane carries its own across the call
+                const bool last = LD::ONCHIP && iter > max_iter;
+                double kdy[VS], kdg[GS];
+                if (last) {
+                    _Pragma("unroll") for (int s = 0; s < VS; s++) kdy[s] = vok[s] ? dyb(s) : 0.0;
+                    _Pragma("unroll") for (int s = 0; s < GS; s++) kdg[s] = gok[s] ? dyg(s) : 0.0;
+                }
                 if (factorize()) {
                     max_iter = 0;
                     status = kRefailMark;
+                }
+                if (last) {  // (after factorize()'s last barrier; R[NL - 1] of an n < NL pattern stays 0)
+                    _Pragma("unroll") for (int s = 0; s < VS; s++)
+                        if (vok[s]) dyb(s) = kdy[s];
+                    _Pragma("unroll") for (int s = 0; s < GS; s++) dyg(s) = kdg[s];
                 }
                 write_v_products();
                 IMPC_SEC(kSecFactor);

@@ -133,6 +133,7 @@ _sig("impc_batch_update_bounds_device", C.c_int, _P, _P, _P)
 _sig("impc_batch_update_matrices", C.c_int, _P, _dp, _dp)
 _sig("impc_batch_update_matrices_device", C.c_int, _P, _P, _P)
 _sig("impc_batch_get_stats", C.c_int, _P, C.POINTER(Stats))
+_sig("impc_batch_get_occupancy", C.c_int, _P, _i64p, _i64p)
 _sig("impc_batch_get_perm", C.c_int, _P, _i64p)
 _sig("impc_batch_set_profiling", C.c_int, _P, C.c_int)
 _sig("impc_batch_get_timings", C.c_int, _P, _dp, _dp, _dp)
@@ -267,7 +268,7 @@ EXPORTED = [
     "impc_replan_view_device", "impc_replan_shape", "impc_replan_advance_device", "impc_batch_follow_plan_device",
     "impc_replan_pack_device", "impc_replan_gather",  # bound in impc.replan
     "impc_copy_rows_device", "impc_batch_update_matrices", "impc_batch_update_matrices_device",
-    "impc_batch_get_persistent",
+    "impc_batch_get_persistent", "impc_batch_get_occupancy",
     "impc_tracks_create", "impc_tracks_destroy", "impc_tracks_push_device", "impc_tracks_reset",
     "impc_detect_gather_device", "impc_detect_gather",  # bound in impc.perception
 ]
@@ -516,7 +517,14 @@ class Batch:
     def stats(self):
         s = Stats()
         _check(lib.impc_batch_get_stats(self.h, C.byref(s)), "impc_batch_get_stats")
-        return {f: getattr(s, f) for f, _ in Stats._fields_}
+        out = {f: getattr(s, f) for f, _ in Stats._fields_}
+        # impc_batch_get_occupancy: resident teams per CU of the last structured launch (0: none
+        # yet) and the LDS bytes of one QP
+        if hasattr(lib, "impc_batch_get_occupancy"):
+            t, l = C.c_int64(0), C.c_int64(0)
+            _check(lib.impc_batch_get_occupancy(self.h, C.byref(t), C.byref(l)), "impc_batch_get_occupancy")
+            out["teams_per_cu"], out["lds_bytes"] = t.value, l.value
+        return out
 
     def set_kernel(self, kernel):
         """impc_batch_set_kernel: KERNEL_AUTO / KERNEL_GENERIC / KERNEL_STRUCTURED."""

@@ -89,6 +89,31 @@ def kinds(lo, hi):
 
 tot = kinds(0, len(ins) - 1)
 print("whole function:", tot)
+# the raised-priority regions (s_setprio N > 0 .. s_setprio 0: the serial stage sweeps): a register
+# reload there sits on the team's critical path
+up, prio = None, []
+for i, (a, t) in enumerate(ins):
+    m = re.match(r"s_setprio\s+(\d+)", t)
+    if not m:
+        continue
+    if int(m.group(1)) > 0:
+        up = i
+    elif up is not None:
+        c = kinds(up, i)
+        print(f"setprio {ins[up][0]:#x}..{a:#x} ({i - up + 1} instructions): scratch_ld {c['scratch_ld']} "
+              f"scratch_st {c['scratch_st']} ds {c['ds']} valu {c['valu']}")
+        prio.append((up, i))
+        up = None
+# the ADMM iteration loop: the innermost loop around each raised-priority region
+shown = set()
+for plo, phi in prio:
+    around = [(lo, hi) for lo, hi in loops if lo <= plo and phi <= hi]
+    if around:
+        lo, hi = min(around, key=lambda x: x[1] - x[0])
+        if (lo, hi) in shown:
+            continue
+        shown.add((lo, hi))
+        print(f"iteration loop {ins[lo][0]:#x}..{ins[hi][0]:#x} ({hi - lo + 1} instructions):", kinds(lo, hi))
 for lo, hi in sorted(loops, key=lambda x: x[1] - x[0], reverse=True):
     if hi - lo < min_len:
         continue
