@@ -35,12 +35,13 @@ EMU64   := $(HARNDIR)/libwave_emu64.so
 SHIMT   := $(HARNDIR)/shim_test
 REPLANX := $(HARNDIR)/replan_example
 DETECTH := $(HARNDIR)/libdetect_harness.so
+MFMODEL := $(HARNDIR)/sweep_mfma_model
 
 .PHONY: all lib oracle harness prof variant clean
 all: lib oracle harness
 lib: $(LIB)
 oracle: $(ORACLE)
-harness: $(HARNESS) $(EMU) $(EMU64) $(SHIMT) $(REPLANX) $(DETECTH)
+harness: $(HARNESS) $(EMU) $(EMU64) $(SHIMT) $(REPLANX) $(DETECTH) $(MFMODEL)
 
 $(LIBDIR)/impc_qp.o: $(CSRC)/impc_qp.hip $(CSRC)/admm_core.hpp $(CSRC)/symbolic.hpp $(CSRC)/mpc_wave.hpp \
 		$(CSRC)/mpc_structure.hpp $(CSRC)/select.hpp $(CSRC)/mpc_build.hpp $(CSRC)/mpc_qp_internal.hpp \
@@ -99,14 +100,14 @@ $(HARNESS): $(ROOT)/tests/native/core_harness.cpp $(CSRC)/admm_core.hpp $(CSRC)/
 		$(ROOT)/tests/native/core_harness.cpp -x c++ $(CSRC)/symbolic.cpp -o $@
 
 $(EMU): $(ROOT)/tests/native/wave_emu.cpp $(CSRC)/mpc_wave.hpp $(CSRC)/admm_core.hpp $(CSRC)/mpc_structure.cpp \
-		$(CSRC)/mpc_structure.hpp
+		$(CSRC)/mpc_structure.hpp $(CSRC)/sweep_mfma_map.hpp
 	@mkdir -p $(HARNDIR)
 	$(HIPCC) -x hip --offload-host-only -std=c++20 -O2 -fPIC -shared -ffp-contract=off \
 		$(ROOT)/tests/native/wave_emu.cpp -x c++ $(CSRC)/mpc_structure.cpp -o $@
 
 # the one-QP-per-wavefront team shape (64 lanes, four variables per lane) in the same emulation
 $(EMU64): $(ROOT)/tests/native/wave_emu.cpp $(CSRC)/mpc_wave.hpp $(CSRC)/admm_core.hpp $(CSRC)/mpc_structure.cpp \
-		$(CSRC)/mpc_structure.hpp
+		$(CSRC)/mpc_structure.hpp $(CSRC)/sweep_mfma_map.hpp
 	@mkdir -p $(HARNDIR)
 	$(HIPCC) -x hip --offload-host-only -std=c++20 -O2 -fPIC -shared -ffp-contract=off -DEMU_NL=64 \
 		$(ROOT)/tests/native/wave_emu.cpp -x c++ $(CSRC)/mpc_structure.cpp -o $@
@@ -128,6 +129,12 @@ $(REPLANX): $(ROOT)/tests/native/replan_example.cpp $(ROOT)/include/impc_qp.h $(
 $(DETECTH): $(ROOT)/tests/native/detect_harness.cpp $(CSRC)/detect_gate.hpp
 	@mkdir -p $(HARNDIR)
 	$(HIPCC) -x hip --offload-host-only -std=c++17 -O2 -fPIC -shared -ffp-contract=off $< -o $@
+
+# host model of the stage recursions on the FP64 matrix instruction against a plain loop (stand-alone,
+# host only; SAN="-fsanitize=address,undefined" for a checked build)
+$(MFMODEL): $(ROOT)/tests/native/sweep_mfma_model.cpp $(CSRC)/sweep_mfma_map.hpp
+	@mkdir -p $(HARNDIR)
+	$(CXX) -O1 -g -std=c++17 -Wall -ffp-contract=off $(SAN) $< -o $@
 
 # kernel experiments (tools/ only): make variant V=name DEFS="-DX=1" -> lib/libimpc_qp_<name>.so,
 # selected at run time with IMPC_LIB_VARIANT=<name>

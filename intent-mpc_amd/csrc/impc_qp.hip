@@ -281,6 +281,14 @@ struct GpuTeam {
         int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
         return __hiloint2double(hi, lo);
     }
+    // One recursion step on the four-block FP64 matrix instruction (mpc_wave.hpp sweep_mfma): c + f v
+    // in the lane's 4x4 block, plus the partner block's result -- lane ^ 4 (row_half_mirror; D is the
+    // same in the four columns of a block) on even steps, lane ^ 8 (row_ror:8) on odd steps.
+    template <bool ODD>
+    __device__ static double mfma_step(double f, double c, double v) {
+        const double d = __builtin_amdgcn_mfma_f64_4x4x4f64(f, v, c, 0, 0, 0);
+        return d + dpp<ODD ? 0x128 : 0x141>(d);
+    }
     // sum over lanes {8i, .., 8i+7}: quad_perm xor 1, quad_perm xor 2, row_half_mirror.  Every
     // stage adds a commuted operand pair, so all 8 lanes hold bitwise the same
     // ((v0+v1)+(v2+v3)) + ((v4+v5)+(v6+v7)).

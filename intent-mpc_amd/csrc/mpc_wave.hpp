@@ -46,6 +46,7 @@
 #include "../../include/impc_qp.h"
 #include "admm_core.hpp"
 #include "mpc_structure.hpp"
+#include "sweep_mfma_map.hpp"
 
 namespace impc {
 
@@ -66,6 +67,16 @@ namespace impc {
 #else
 #define IMPC_PRIO_UP() ((void)0)
 #define IMPC_PRIO_DOWN() ((void)0)
+#endif
+// The fully unrolled default-horizon stage recursions on the four-block FP64 matrix instruction
+// (sweep_mfma below) instead of the 8x8 lane grid; device code only, 0 = the lane grid (A/B variants).
+#ifndef IMPC_SWEEP_MFMA
+#define IMPC_SWEEP_MFMA 1
+#endif
+#if IMPC_SWEEP_MFMA && defined(__HIP_DEVICE_COMPILE__)
+#define IMPC_SWEEP_MFMA_DEV 1
+#else
+#define IMPC_SWEEP_MFMA_DEV 0
 #endif
 #ifndef IMPC_DUP
 #define IMPC_DUP -1
@@ -984,8 +995,9 @@ struct WaveQP {
                     else
                         E[8 * i + j] = s;
                     // recursion layout: lane (i,j) of step k reads F_k[j][i] when the column index
-                    // sits on i (k even), F_k[i][j] otherwise
-                    Fm[64 * k + 8 * i + j] = !(k & 1) ? G[13 * j + i] : G[13 * i + j];
+                    // sits on i (k even), F_k[i][j] otherwise (mfmap::f_slot); stored negated, so a
+                    // recursion step is c + (-F) v in one fma or one matrix instruction
+                    Fm[64 * k + 8 * i + j] = -(!(k & 1) ? G[13 * j + i] : G[13 * i + j]);
                 }
                 _Pragma("unroll") for (int s = 0; s < VS; s++) {
                     if (!vok[s]) continue;
@@ -1009,9 +1021,9 @@ struct WaveQP {
         return bad;
     }
 
-    // F_k[r][c] from the recursion layout (factorize stores even stages' blocks transposed)
+    // F_k[r][c] from the recursion layout (factorize stores -F_k, even stages' blocks transposed)
     IMPC_WF static double f_el(const double *Fm, int k, int r, int c) {
-        return !(k & 1) ? Fm[64 * k + 8 * c + r] : Fm[64 * k + 8 * r + c];
+        return -(!(k & 1) ? Fm[64 * k + 8 * c + r] : Fm[64 * k + 8 * r + c]);  // mfmap::f_slot
     }
 
     // The chunk operators (CHUNK): wave 0 / 1 the forward chunks 1 / 2 (steps CL..2CL-1 /
@@ -1099,13 +1111,15 @@ struct WaveQP {
         wv.sync();
     }
 
-    // One step of a stage recursion on the 8x8 lane grid: returns c - F v as R(c / 8 - f v), R the
-    // strided (STRIDE) or contiguous 8-lane sum.  The sweeps' inputs c come pre-scaled by 1/8
-    // (exact: S1 stores t / 8, S3 the state part of e / 8), so the subtraction rides in the
-    // product's FMA: one instruction and one dependent operation less per step on the serial chain.
+    // One step of a stage recursion on the 8x8 lane grid: returns c - F v as R(c / 8 + nf v), R the
+    // strided (STRIDE) or contiguous 8-lane sum and nf the stored -F element.  The sweeps' inputs c
+    // come pre-scaled by kSweepPre = 1/8 (exact: S1 stores t / 8, S3 the state part of e / 8), so the
+    // subtraction rides in the product's FMA: one instruction and one dependent operation less per
+    // step on the serial chain.  (The matrix-instruction form, sweep_mfma, reads the same inputs.)
+    static constexpr double kSweepPre = 0.125;
     template <bool STRIDE>
-    IMPC_WF double rstep(double f, double c8, double v) {
-        const double p = __builtin_fma(-f, v, c8);
+    IMPC_WF double rstep(double nf, double c8, double v) {
+        const double p = __builtin_fma(nf, v, c8);
         return STRIDE ? wv.sum_stride8(p) : wv.sum_contig8(p);
     }
 
@@ -1150,6 +1164,65 @@ struct WaveQP {
         }
     }
 
+#if IMPC_SWEEP_MFMA_DEV
+    // The select of capm by a lane mask given as a constant (mfmap::keep_mask)
+    IMPC_WF static void capk(double &d, double r, uint64_t msk) {
+        int lo = __double2loint(d), hi = __double2hiint(d);
+        asm("v_cndmask_b32 %0, %0, %1, %2" : "+v"(lo) : "v"(__double2loint(r)), "s"(msk));
+        asm("v_cndmask_b32 %0, %0, %1, %2" : "+v"(hi) : "v"(__double2hiint(r)), "s"(msk));
+        d = __hiloint2double(hi, lo);
+    }
+    // A fully unrolled sweep of WC steps on v_mfma_f64_4x4x4_4b_f64 (sweep_mfma_map.hpp: layout, block
+    // numbering, why no transpose sits on the chain).  FWD: a_{k+1} = t_{k+1} - F_k a_k, step m is
+    // stage k = m and produces stage m + 1; else x_k = e_k - F_k' x_{k+1}, step m is stage
+    // k = WC - 1 - m.  A step is the instruction (A the stored -F_k element of the lane's block, B the
+    // running vector, C the input c), one DPP move of the partner block's D and one add.  cb holds
+    // c * kSweepPre = c / 8 and both blocks of a row add it, so the chain runs in units of
+    // 2 kSweepPre = 1/4: v / 4 = 2 (c / 8) - F (v / 4), exact, and the captured steps are scaled back
+    // when they are stored after the sweep.  (Keeping F's sign and negating every other step's c
+    // instead was measured: 182.4-182.7 ms per config-3 launch against 171.8-171.9 for this form
+    // and the parent's 184.0, profiles/r09/kernel_ab.txt.)  Capture and prefetch distance as on the
+    // lane grid; the per-lane offsets come from the opaque lane index here, not from outside the
+    // ADMM loop.
+    template <int WC, bool FWD>
+    IMPC_WF void sweep_mfma(const double *cb, double *ob) {
+        const double *Fm = lds + LD::F_OFF;
+        const int l = lane_o() & 63;
+        constexpr int k0 = FWD ? 0 : WC - 1, k1 = FWD ? 1 : (WC - 2 > 0 ? WC - 2 : 0);  // stages of steps 0, 1
+        const int fse = mfmap::a_slot(l, false, FWD, !(k0 & 1)), fso = mfmap::a_slot(l, true, FWD, !(k1 & 1));
+        const int oe = mfmap::out_idx(l, false), oo = mfmap::out_idx(l, true);
+        auto fst = [](int m) { const int k = FWD ? m : WC - 1 - m; return 64 * (k > 0 ? k : 0); };
+        auto cst = [](int m) { const int k = FWD ? m + 1 : WC - 1 - m; return 13 * (k > 0 ? k : 0); };
+        double v = 2.0 * cb[13 * (FWD ? 0 : WC) + mfmap::in_idx(l, false)];  // (c / 8) (1/4) / (1/8)
+        // (F, c) of the next even / odd step, loaded two steps ahead (forward reads past the last
+        // stage stay inside the LDS buffers and are never used)
+        double fe = Fm[fst(0) + fse], ce = cb[cst(0) + oe], fo = Fm[fst(1) + fso], co = cb[cst(1) + oo];
+        double c0[CQ], c1[CQ];
+        _Pragma("unroll") for (int q = 0; q < CQ; q++) c0[q] = c1[q] = 0.0;
+        _Pragma("unroll") for (int m = 0; m < WC; m += 2) {
+            const double f0 = fe, e0 = ce;
+            fe = Fm[fst(m + 2) + fse];
+            ce = cb[cst(m + 2) + oe];
+            v = wv.template mfma_step<false>(f0, e0, v);
+            capk(c0[m >> 4], v, mfmap::keep_mask((m >> 1) & 7, false));
+            if (m + 1 < WC) {
+                const double f1 = fo, e1 = co;
+                fo = Fm[fst(m + 3) + fso];
+                co = cb[cst(m + 3) + oo];
+                v = wv.template mfma_step<true>(f1, e1, v);
+                capk(c1[m >> 4], v, mfmap::keep_mask((m >> 1) & 7, true));
+            }
+        }
+        const int he = mfmap::other(l, false), ho = mfmap::other(l, true);
+        constexpr double back = 1.0 / (2.0 * kSweepPre);
+        _Pragma("unroll") for (int q = 0; q < CQ; q++) {
+            const int m0 = 16 * q + 2 * he, m1 = 16 * q + 2 * ho + 1;
+            if (m0 < WC) ob[13 * (FWD ? m0 + 1 : WC - 1 - m0) + oe] = back * c0[q];
+            if (m1 < WC) ob[13 * (FWD ? m1 + 1 : WC - 1 - m1) + oo] = back * c1[q];
+        }
+    }
+#endif
+
     // Forward steps o .. o + WC - 1 (o even) from a_o = a at index i, fully unrolled: the results
     // a_{o+1} .. a_{o+WC} stored to rb when CAP, the last one returned (every lane (i, j) holds
     // a_{o+WC}[i] or [j] by its parity).
@@ -1184,9 +1257,12 @@ struct WaveQP {
     // S2 body: a_{k+1} = t_{k+1} - F_k a_k for k = 0..W-1 (WC = W, or 0 for a runtime W).
     template <int WC>
     IMPC_WF void fwd_sweep(const double *tb, double *rb, int W) {
+#if IMPC_SWEEP_MFMA_DEV
+        if constexpr (WC > 0) return sweep_mfma<WC, true>(tb, rb);
+#endif
         const double *Fm = lds + LD::F_OFF;
         const int lo = lane_o(), l = lo & 63, i = l >> 3, j = l & 7;  // opaque: see lane_o
-        double a = 8.0 * tb[i];  // a_0 = t_0 (tb holds t / 8)
+        double a = (1.0 / kSweepPre) * tb[i];  // a_0 = t_0 (tb holds t / 8)
         // (F, t) of the next even / odd step, loaded two steps ahead (reads past the last stage
         // stay inside the LDS buffers and are never used)
         double fe = Fm[l], te = tb[13 + j], fo = Fm[64 + l], to = tb[26 + i];
@@ -1264,11 +1340,14 @@ struct WaveQP {
     // contiguous (even k) reductions; x_k sits at index j (odd k) / i (even k).  WC as above.
     template <bool ODD, int WC>
     IMPC_WF void bwd_sweep(const double *eb, double *xb, int W) {
+#if IMPC_SWEEP_MFMA_DEV
+        if constexpr (WC > 0) return sweep_mfma<WC, false>(eb, xb);
+#endif
         const double *Fm = lds + LD::F_OFF;
         const int lo = lane_o(), l = lo & 63, i = l >> 3, j = l & 7;
         if constexpr (WC > 0) W = WC;
         // x_W = e_W: W = (W-1)+1 has the opposite parity of the first step (eb holds e[:8] / 8)
-        double x = 8.0 * eb[13 * W + (ODD ? i : j)];
+        double x = (1.0 / kSweepPre) * eb[13 * W + (ODD ? i : j)];
         const int k1 = W - 2 > 0 ? W - 2 : 0;
         double fa = Fm[64 * (W - 1) + l], ea = eb[13 * (W - 1) + (ODD ? j : i)];
         double fb = Fm[64 * k1 + l], ebv = eb[13 * k1 + (ODD ? i : j)];
@@ -1484,7 +1563,7 @@ struct WaveQP {
                 _Pragma("unroll") for (int cc = 0; cc < 5; cc++) rv[cc] = rp[cc];
                 IMPC_LOADS_FIRST(5, 12);
                 _Pragma("unroll") for (int cc = 0; cc < 5; cc++) t -= cp[s][cc] * rv[cc];
-                tb[v] = 0.125 * t;  // the forward sweep's input, pre-scaled (rstep)
+                tb[v] = kSweepPre * t;  // the forward sweep's input, pre-scaled (rstep)
             }
             wv.lsync();
         }
@@ -1524,7 +1603,7 @@ struct WaveQP {
                 double e = 0.0;
                 _Pragma("unroll") for (int cc = 0; cc < 13; cc++) e += ainv[s][cc] * rv[cc];
                 // the state part pre-scaled for the backward sweep (rstep); S5 reads the controls' e
-                eb[NL * s + L] = vr_[s] < 8 ? 0.125 * e : e;
+                eb[NL * s + L] = vr_[s] < 8 ? kSweepPre * e : e;
             }
             wv.lsync();
         }
@@ -1532,7 +1611,7 @@ struct WaveQP {
         IMPC_REP(kSecBwd) {
             // S4: backward 8-dim recursion x_k[:8] = e_k[:8] - F_k' x_{k+1}[:8] on the same grid and
             // stored layout: even steps reduce over j (contiguous), odd steps over i (strided).
-            if (L < 8) xb[13 * W + L] = 8.0 * eb[13 * W + L];
+            if (L < 8) xb[13 * W + L] = (1.0 / kSweepPre) * eb[13 * W + L];
             if constexpr (CHUNK && NCH == 5) {
                 bwd_chunked5(eb, xb);
             } else if constexpr (CHUNK) {

@@ -17,7 +17,26 @@
 //      the 8 operands by v_mov_b64_dpp row_newbcast, 4 mul + 4 fma + depth-2 adds in the lane;
 //      fully unrolled, captured in registers (copy l >> 3 keeps step m when m % 8 == l >> 3)
 //   9  as 8 with an LDS store of each stage by lanes 0..7 (runtime loop)
+//  10  as 1 with two independent chains interleaved in one instruction stream
+//
+// The four-block FP64 matrix instruction v_mfma_f64_4x4x4_4b_f64 (one f64 per lane for A, B and C/D),
+// printed after the table above in the same run:
+//   - its operand layout, found by feeding unit inputs (k_layout).  On gfx950, with lane = x + 4 b + 16 q
+//     and b the block: A[i][k] sits in lane i + 4 b + 16 k, B[k][j] in lane j + 4 b + 16 k, C[i][j] and
+//     D[i][j] in lane j + 4 b + 16 i; an element's four products are added to C in k-ascending fma order
+//     (the sweeps below match that chain bit for bit);
+//   - issue-to-issue cycles of dependent chains of it (k_lat);
+//   - both W-step sweeps, capture and stores included, on host-made random F, t (km):
+//      11 / 12  the lane grid as the kernel runs it (fma(-f, v, c / 8), constant-mask capture), forward /
+//               backward
+//      13 / 14  the step as one instruction: block (r, c) takes -F's 4x4 block, B = v[4 c + k] in all four
+//               columns, C = c[4 r + i] / 2 in both blocks of a row, v'[4 r + i] = D(r, 0) + D(r, 1) by one
+//               row DPP move + add; the block numbering alternates between even and odd steps (see the
+//               mf_* maps) so that the sum lands where the next step's B wants it
+//      15 / 16  as 13 / 14 with the capture select written in C++ (inverse ballot of the constant mask)
+//     and their difference from a long-double evaluation next to the lane grid's.
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdio>
 
 constexpr int W = 19, REP = 32;
@@ -229,6 +248,303 @@ __global__ void kr(double *o, unsigned long long *cyc, int Wr) {
     if (threadIdx.x == 0) cyc[MODE] = (c1 - c0) / (REP * W);
 }
 
+// ---- modes 11..14: the four-block v_mfma_f64_4x4x4_4b_f64 -------------------------------------
+typedef unsigned long long u64;
+__device__ double mfma4(double a, double b, double c) { return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0); }
+
+// Operand layout: A = 1 in lane la only, B = 1 in lane lb only, C = 0; msk[64 la + lb] = the lanes
+// whose D is not zero (same block and same k: row i of A's lane, column j of B's lane).
+__global__ void k_layout(u64 *msk) {
+    const int l = threadIdx.x;
+    for (int la = 0; la < 64; la++)
+        for (int lb = 0; lb < 64; lb++) {
+            const double d = mfma4(l == la ? 1.0 : 0.0, l == lb ? 1.0 : 0.0, 0.0);
+            const u64 m = __ballot(d != 0.0);
+            if (l == 0) msk[64 * la + lb] = m;
+        }
+}
+
+// Issue-to-issue cycles of dependent chains of the instruction (64 in a row, compiler's own waits):
+// 0 D -> C, 1 D -> B, 2 D -> v_add_f64 -> B, 3 D -> row DPP pair sum (2 mov_dpp + add) -> B
+template <int V>
+__global__ void k_lat(double *o, u64 *cyc) {
+    const int l = threadIdx.x;
+    const double a = 0.001 * l, b = 0.5 + 0.001 * l, c = 0.25;
+    u64 c0 = 0;
+    double x = b, y = c;
+    for (int rep = -1; rep < REP; rep++) {
+        if (rep == 0) c0 = __builtin_amdgcn_s_memtime();
+        _Pragma("unroll") for (int q = 0; q < 64; q++) {
+            if (V == 0) y = mfma4(a, x, y);
+            if (V == 1) x = mfma4(a, x, y);
+            if (V == 2) x = mfma4(a, x, y) + 1.0;
+            if (V == 3) {
+                const double d = mfma4(a, x, y);
+                x = d + dpp<0x141, true>(d);
+            }
+        }
+        asm volatile("" : "+v"(x), "+v"(y));
+    }
+    const u64 c1 = __builtin_amdgcn_s_memtime();
+    if (l == 0) cyc[V] = (c1 - c0) * 10 / (REP * 64);
+    o[l] = x + y;
+}
+
+// ---- lane and block maps of the 4x4x4 form (plain integer functions: they also compile for the host)
+// Layout found on gfx950 (k_layout): lane = x + 4 b + 16 q with b the block;
+//   A[i][k] of block b sits in lane i + 4 b + 16 k, B[k][j] in lane j + 4 b + 16 k, D[i][j] (and C) in
+//   lane j + 4 b + 16 i.
+// A step v' = c - M v (M 8x8 as 2x2 blocks of 4x4) is one instruction: block b carries M's block
+// (r, c'), B = v[4 c' + k] in every column j, C = S c[4 r + i] in every column (S = kMfmaScale = 1/2:
+// both blocks of a row r carry half of c, so no lane needs a zero), and v'[4 r + i] = D(r,0) + D(r,1).
+// Even steps number the blocks b = 2 r + c': the partner is lane ^ 4 (row_half_mirror, D is the same
+// in all four columns) and the sum leaves v'[4 (b >> 1) + q] in lane (x, b, q) -- which is the B
+// operand of an odd step, whose blocks are numbered b = r + 2 c' (partner lane ^ 8, row_ror:8),
+// leaving v'[4 (b & 1) + q]: the even step's B again.  No transpose on the chain.
+constexpr double kMfmaScale = 0.5;
+__host__ __device__ constexpr int mf_x(int l) { return l & 3; }
+__host__ __device__ constexpr int mf_b(int l) { return (l >> 2) & 3; }
+__host__ __device__ constexpr int mf_q(int l) { return l >> 4; }
+__host__ __device__ constexpr int mf_r(int l, bool odd) { return odd ? mf_b(l) & 1 : mf_b(l) >> 1; }  // block row
+__host__ __device__ constexpr int mf_c(int l, bool odd) { return odd ? mf_b(l) >> 1 : mf_b(l) & 1; }  // block column
+// slot (row-major 8 r + c of F_k) that lane l feeds to A: -F_k forward, -F_k' backward
+__host__ __device__ constexpr int mf_fslot(int l, bool odd, bool fwd) {
+    const int row = 4 * mf_r(l, odd) + mf_x(l), col = 4 * mf_c(l, odd) + mf_q(l);
+    return fwd ? 8 * row + col : 8 * col + row;
+}
+__host__ __device__ constexpr int mf_in(int l, bool odd) { return 4 * mf_c(l, odd) + mf_q(l); }   // element of v in B
+__host__ __device__ constexpr int mf_out(int l, bool odd) { return 4 * mf_r(l, odd) + mf_q(l); }  // element of c, v'
+// the 8 lanes sharing an output element differ in this index; lane with other == (m / 2) % 8 keeps step m
+__host__ __device__ constexpr int mf_other(int l, bool odd) { return mf_x(l) + 4 * mf_c(l, odd); }
+__host__ __device__ constexpr u64 mf_mask(int v, bool odd) {
+    return odd ? 0x0001000100010001ull * (0x11ull << ((v & 3) + 8 * (v >> 2))) : 0x0101010101010101ull << v;
+}
+
+template <bool IB = false>
+__device__ void capc(double &d, double r, u64 MSK) {
+    if (IB) {  // the same select, visible to the compiler's scheduler and hazard counting
+        d = __builtin_amdgcn_inverse_ballot_w64(MSK) ? r : d;
+        return;
+    }
+    int lo = __double2loint(d), hi = __double2hiint(d);
+    asm("v_cndmask_b32 %0, %0, %1, %2" : "+v"(lo) : "v"(__double2loint(r)), "s"(MSK));
+    asm("v_cndmask_b32 %0, %0, %1, %2" : "+v"(hi) : "v"(__double2hiint(r)), "s"(MSK));
+    d = __hiloint2double(hi, lo);
+}
+
+// Modes 11 / 12: the lane grid as the kernel runs it (fma(-f, v, c / 8), 8-lane sums, constant-mask
+// capture, stores after the sweep), forward / backward.  Modes 13 / 14: the 4x4x4 form.  F, t from the
+// host (gF row-major F_k, gt stride 13), results of wave 0 to gout for the arithmetic check.
+template <int MODE>
+__global__ void km(const double *gF, const double *gt, double *gout, double *o, u64 *cyc) {
+    __shared__ double F[8][64 * (W + 3)];
+    __shared__ double t[8][13 * (W + 4)], out[8][13 * (W + 4)];
+    constexpr bool MF = MODE >= 13, FWD = (MODE & 1) != 0, IB = MODE >= 15;
+    const int wv = threadIdx.x >> 6, l = threadIdx.x & 63, i = l >> 3, j = l & 7;
+    for (int p = l; p < 64 * (W + 3); p += 64) {
+        const int k = p >> 6, e = p & 63;
+        // lane grid: even k transposed (the kernel's f_el); 4x4x4: -F_k row-major
+        F[wv][p] = MF ? -gF[p] : (!(k & 1) ? gF[64 * k + 8 * (e & 7) + (e >> 3)] : gF[p]);
+    }
+    for (int p = l; p < 13 * (W + 4); p += 64) t[wv][p] = gt[p] * (MF ? kMfmaScale : 0.125), out[wv][p] = 0.0;
+    __syncthreads();
+    const double *Fm = F[wv], *tb = t[wv];
+    double *rb = out[wv];
+    double acc = 0.0;
+    u64 c0 = 0;
+    for (int rep = -1; rep < REP; rep++) {
+        if (rep == 0) c0 = __builtin_amdgcn_s_memtime();
+        double ce[2] = {0, 0}, co[2] = {0, 0};
+        if (!MF) {
+            // even steps m: strided sum when the stage k is even (forward k = m, backward k = W-1-m)
+            constexpr bool S0 = FWD ? true : ((W - 1) & 1) == 0 ? false : true;  // bwd: odd k strided
+            const int i0 = S0 ? i : j, j0 = S0 ? j : i;                         // even step: in at i0, out at j0
+            double a = 8.0 * tb[FWD ? i0 : 13 * W + i0];
+            auto fk = [&](int m) { const int k = FWD ? m : W - 1 - m; return 64 * (k > 0 ? k : 0) + l; };
+            auto tk = [&](int m) { const int k = FWD ? m + 1 : W - 1 - m; return 13 * (k > 0 ? k : 0); };
+            double fe = Fm[fk(0)], te = tb[tk(0) + j0], fo = Fm[fk(1)], to = tb[tk(1) + i0];
+            _Pragma("unroll") for (int m = 0; m < W; m += 2) {
+                const double f0 = fe, t0 = te;
+                fe = Fm[fk(m + 2)];
+                te = tb[tk(m + 2) + j0];
+                const double p0 = __builtin_fma(-f0, a, t0);
+                a = S0 ? strided<true>(p0) : contig<true>(p0);
+                const u64 mi = 0xFFull << (8 * ((m >> 1) & 7)), mj = 0x0101010101010101ull << ((m >> 1) & 7);
+                capc(ce[m >> 4], a, S0 ? mi : mj);
+                if (m + 1 < W) {
+                    const double f1 = fo, t1 = to;
+                    fo = Fm[fk(m + 3)];
+                    to = tb[tk(m + 3) + i0];
+                    const double p1 = __builtin_fma(-f1, a, t1);
+                    a = S0 ? contig<true>(p1) : strided<true>(p1);
+                    capc(co[m >> 4], a, S0 ? mj : mi);
+                }
+            }
+            _Pragma("unroll") for (int q = 0; q < 2; q++) {
+                const int m0 = 16 * q + 2 * i0, m1 = 16 * q + 2 * j0 + 1;
+                if (m0 < W) rb[13 * (FWD ? m0 + 1 : W - 1 - m0) + j0] = ce[q];
+                if (m1 < W) rb[13 * (FWD ? m1 + 1 : W - 1 - m1) + i0] = co[q];
+            }
+            acc += a;
+        } else {
+            const int fse = mf_fslot(l, false, FWD), fso = mf_fslot(l, true, FWD);
+            const int oe = mf_out(l, false), oo = mf_out(l, true);
+            double a = (1.0 / kMfmaScale) * tb[(FWD ? 0 : 13 * W) + mf_in(l, false)];
+            auto fk = [&](int m) { const int k = FWD ? m : W - 1 - m; return 64 * (k > 0 ? k : 0); };
+            auto tk = [&](int m) { const int k = FWD ? m + 1 : W - 1 - m; return 13 * (k > 0 ? k : 0); };
+            double fe = Fm[fk(0) + fse], te = tb[tk(0) + oe], fo = Fm[fk(1) + fso], to = tb[tk(1) + oo];
+            _Pragma("unroll") for (int m = 0; m < W; m += 2) {
+                const double f0 = fe, t0 = te;
+                fe = Fm[fk(m + 2) + fse];
+                te = tb[tk(m + 2) + oe];
+                const double d0 = mfma4(f0, a, t0);
+                a = d0 + dpp<0x141, true>(d0);
+                capc<IB>(ce[m >> 4], a, mf_mask((m >> 1) & 7, false));
+                if (m + 1 < W) {
+                    const double f1 = fo, t1 = to;
+                    fo = Fm[fk(m + 3) + fso];
+                    to = tb[tk(m + 3) + oo];
+                    const double d1 = mfma4(f1, a, t1);
+                    a = d1 + dpp<0x128, true>(d1);
+                    capc<IB>(co[m >> 4], a, mf_mask((m >> 1) & 7, true));
+                }
+            }
+            _Pragma("unroll") for (int q = 0; q < 2; q++) {
+                const int m0 = 16 * q + 2 * mf_other(l, false), m1 = 16 * q + 2 * mf_other(l, true) + 1;
+                if (m0 < W) rb[13 * (FWD ? m0 + 1 : W - 1 - m0) + oe] = ce[q];
+                if (m1 < W) rb[13 * (FWD ? m1 + 1 : W - 1 - m1) + oo] = co[q];
+            }
+            acc += a;
+        }
+    }
+    const u64 c1 = __builtin_amdgcn_s_memtime();
+    o[threadIdx.x] = acc;
+    if (threadIdx.x == 0) cyc[MODE] = (c1 - c0) * 10 / (REP * W);
+    if (wv == 0)
+        for (int p = l; p < 13 * (W + 4); p += 64) gout[p] = rb[p];
+}
+
+// Host references of both sweeps on (gF, gt): REF 0 long double, REF 1 / 2 the 4x4x4 form's value if the
+// instruction runs D = fma(A[i][3], B[3], .. fma(A[i][0], B[0], C)) (k ascending) / k descending per
+// block, followed by the pair sum.  Results in the sweeps' layout (stride 13).
+template <int REF>
+static void host_sweep(const double *gF, const double *gt, bool fwd, long double *res) {
+    long double v[8], vn[8];
+    for (int r = 0; r < 8; r++) v[r] = gt[(fwd ? 0 : 13 * W) + r];
+    for (int m = 0; m < W; m++) {
+        const int k = fwd ? m : W - 1 - m, st = fwd ? m + 1 : k;
+        for (int r = 0; r < 8; r++) {
+            auto fe = [&](int c) { return fwd ? gF[64 * k + 8 * r + c] : gF[64 * k + 8 * c + r]; };
+            if (REF == 0) {
+                long double s = gt[13 * st + r];
+                for (int c = 0; c < 8; c++) s -= (long double)fe(c) * v[c];
+                vn[r] = s;
+            } else {
+                double d[2];
+                for (int cb = 0; cb < 2; cb++) {
+                    d[cb] = gt[13 * st + r] * kMfmaScale;
+                    for (int kk = 0; kk < 4; kk++) {
+                        const int c = 4 * cb + (REF == 1 ? kk : 3 - kk);
+                        d[cb] = __builtin_fma(-fe(c), (double)v[c], d[cb]);
+                    }
+                }
+                vn[r] = d[0] + d[1];
+            }
+        }
+        for (int r = 0; r < 8; r++) res[13 * st + r] = v[r] = vn[r];
+    }
+}
+
+static int mfma4_modes(double *o) {
+    // operand layout
+    u64 *dm, *dc, hm[4096], hc[20] = {};
+    if (hipMalloc(&dm, sizeof(hm)) || hipMalloc(&dc, sizeof(hc))) return 1;
+    hipLaunchKernelGGL(k_layout, 1, 64, 0, 0, dm);
+    if (hipMemcpy(hm, dm, sizeof(hm), hipMemcpyDeviceToHost)) return 1;
+    int bad = 0;
+    for (int la = 0; la < 64; la++)
+        for (int lb = 0; lb < 64; lb++) {
+            const bool same = mf_b(la) == mf_b(lb) && mf_q(la) == mf_q(lb);  // same block, same k
+            const u64 want = same ? 1ull << (mf_x(lb) + 4 * mf_b(la) + 16 * mf_x(la)) : 0;
+            bad += hm[64 * la + lb] != want;
+        }
+    printf("-- v_mfma_f64_4x4x4_4b_f64 operand layout\n");
+    printf("A[i][k] blk b: lane i+4b+16k, B[k][j]: lane j+4b+16k, D[i][j]: lane j+4b+16i -- %s (%d of 4096 differ)\n",
+           bad ? "NOT what the hardware does" : "confirmed", bad);
+    if (bad)
+        for (int la = 0; la < 64; la++) {
+            u64 sa = 0, sb = 0, pl = 0;  // D lanes fed by A lane la, by B lane la; B lanes that meet A lane la
+            for (int x = 0; x < 64; x++) {
+                sa |= hm[64 * la + x], sb |= hm[64 * x + la];
+                if (hm[64 * la + x]) pl |= 1ull << x;
+            }
+            printf("lane %2d: A feeds D %016llx, meets B lanes %016llx; B feeds D %016llx\n", la, sa, pl, sb);
+        }
+    // dependent-issue latency
+    for (int it = 0; it < 2; it++) {
+        hipLaunchKernelGGL(k_lat<0>, 1, 64, 0, 0, o, dc);
+        hipLaunchKernelGGL(k_lat<1>, 1, 64, 0, 0, o, dc);
+        hipLaunchKernelGGL(k_lat<2>, 1, 64, 0, 0, o, dc);
+        hipLaunchKernelGGL(k_lat<3>, 1, 64, 0, 0, o, dc);
+    }
+    if (hipMemcpy(hc, dc, sizeof(hc), hipMemcpyDeviceToHost)) return 1;
+    const char *ln[] = {"D -> C", "D -> B", "D -> v_add_f64 -> B", "D -> 2 mov_dpp + add -> B"};
+    printf("-- dependent chains of the instruction, cycles per link (1 wavefront)\n");
+    for (int v = 0; v < 4; v++) printf("%-28s %5.1f\n", ln[v], hc[v] / 10.0);
+    // the sweeps
+    constexpr int NF = 64 * (W + 3), NT = 13 * (W + 4);
+    static double gF[NF], gt[NT], ho[6][NT];
+    static long double ref[2][3][NT];
+    u64 s = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&]() { s = s * 6364136223846793005ull + 1442695040888963407ull; return (double)(s >> 11) / 9007199254740992.0 - 0.5; };
+    for (double &f : gF) f = 0.24 * rnd();
+    for (double &t : gt) t = rnd();
+    double *dF, *dt, *dout;
+    if (hipMalloc(&dF, sizeof(gF)) || hipMalloc(&dt, sizeof(gt)) || hipMalloc(&dout, sizeof(gt))) return 1;
+    if (hipMemcpy(dF, gF, sizeof(gF), hipMemcpyHostToDevice) || hipMemcpy(dt, gt, sizeof(gt), hipMemcpyHostToDevice)) return 1;
+    for (int d = 0; d < 2; d++) {
+        host_sweep<0>(gF, gt, d == 0, ref[d][0]);
+        host_sweep<1>(gF, gt, d == 0, ref[d][1]);
+        host_sweep<2>(gF, gt, d == 0, ref[d][2]);
+    }
+    const char *mn[] = {"grid, kernel form, forward", "grid, kernel form, backward", "mfma 4x4x4, forward", "mfma 4x4x4, backward",
+                        "mfma 4x4x4, C++ select, fwd", "mfma 4x4x4, C++ select, bwd"};
+    for (int threads : {64, 512}) {
+        for (int it = 0; it < 2; it++)
+            for (int m = 0; m < 6; m++) {
+                if (m == 0) hipLaunchKernelGGL(km<11>, 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 1) hipLaunchKernelGGL(km<12>, 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 2) hipLaunchKernelGGL(km<13>, 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 3) hipLaunchKernelGGL(km<14>, 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 4) hipLaunchKernelGGL(km<15>, 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 5) hipLaunchKernelGGL(km<16>, 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (hipMemcpy(ho[m], dout, sizeof(gt), hipMemcpyDeviceToHost)) return 1;
+            }
+        if (hipMemcpy(hc, dc, sizeof(hc), hipMemcpyDeviceToHost)) return 1;
+        printf("-- %d lanes (%d wave(s) per SIMD), capture included\n", threads, threads > 256 ? 2 : 1);
+        for (int m = 0; m < 6; m++)
+            printf("%-28s %5.1f cyc/step  (%.3f x the grid)\n", mn[m], hc[11 + m] / 10.0, (double)hc[11 + m] / hc[11 + (m & 1)]);
+    }
+    // arithmetic (wave 0 of the last run): max |v - long double| / max |long double| over all stages
+    printf("-- arithmetic, W = %d steps on random F, t\n", W);
+    for (int m = 0; m < 6; m++) {
+        const int d = m & 1, s0 = d == 0 ? 1 : 0;
+        long double mx = 0, df = 0;
+        int nb[3] = {0, 0, 0};
+        for (int st = s0; st < s0 + W; st++)
+            for (int r = 0; r < 8; r++) {
+                const int p = 13 * st + r;
+                mx = fmaxl(mx, fabsl(ref[d][0][p]));
+                df = fmaxl(df, fabsl(ho[m][p] - ref[d][0][p]));
+                for (int q = 1; q < 3; q++) nb[q] += ho[m][p] != (double)ref[d][q][p];
+            }
+        printf("%-28s rel diff from long double %.3Le", mn[m], df / mx);
+        if (m >= 2) printf("; of %d values %d differ from the k-ascending fma chain, %d from k-descending", 8 * W, nb[1], nb[2]);
+        printf("\n");
+    }
+    return 0;
+}
+
 int main() {
     double *o;
     unsigned long long *c, h[11] = {};
@@ -255,5 +571,5 @@ int main() {
         printf("-- %d lanes (%d wave(s) per SIMD)\n", threads, threads > 256 ? 2 : 1);
         for (int m = 0; m < 11; m++) printf("%-28s %llu cyc/step\n", nm[m], h[m]);
     }
-    return 0;
+    return mfma4_modes(o);
 }
