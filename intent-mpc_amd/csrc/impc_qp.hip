@@ -65,7 +65,7 @@ constexpr int kBlock = 64;  // generic path: one wavefront per workgroup, one QP
 constexpr int kTile = 64;   // transpose tile edge
 // Structured path team shapes, keyed by the variable slots per lane VS:
 //   VS = 1  team shape: one QP per 256-lane workgroup (one variable per lane), two teams per CU,
-//           or three (a second instance of the kernel, 168 VGPRs) for a launch of more than
+//           or three (a second instance of the kernel, 168 VGPRs, WaveQP DENSE) for a launch of more than
 //           kDenseMinPerCu QPs per CU whose batches' LDS fits a third of the CU (n <= 256: the
 //           reference's default horizon N = 20)
 //   VS = 3  long shape: 256 lanes, three variables per lane, one team per CU (n <= 768)
@@ -237,7 +237,10 @@ __global__ __launch_bounds__(kBlock) void k_update_bounds(impc::DevSym sy, impc:
 #ifndef IMPC_LCOMB
 #define IMPC_LCOMB 1
 #endif
-template <int NL>
+// LEAN (the three-teams-per-CU instance): a reduction's LDS slot is addressed from a thread index the
+// optimiser cannot see through, so the address is formed where it is used and no register (or spill
+// slot, reloaded inside the ADMM loop's time-limit test) carries it across the loop.
+template <int NL, bool LEAN = false>
 struct GpuTeam {
     double *red;  // >= NL/64 doubles of LDS
     __device__ int lane() const { return (int)threadIdx.x; }
@@ -375,7 +378,7 @@ struct GpuTeam {
     template <int KM, int KS>
     __device__ void reduce(double (&mx)[KM], double *sm) {
         constexpr int K1 = (KM + 1) / 2, K2 = (K1 + 1) / 2, KT = KM + KS;
-        static_assert(KT * (NL / 64) <= impc::kRedLen, "team reduction scratch (WaveLds RED_OFF)");
+        static_assert(KT * (NL / 64) <= impc::kRedUsed, "team reduction scratch (WaveLds RED_OFF)");
         auto vmax = [](double a, double b) { return b > a ? b : a; };
         double h[K1], q[K2];
         _Pragma("unroll") for (int k = 0; k < K1; k++) {
@@ -393,7 +396,9 @@ struct GpuTeam {
             q[k] = vmax(t, dpp<0x128>(t));  // row_ror:8
         }
         _Pragma("unroll") for (int k = 0; k < KS; k++) sm[k] = wave_sum(sm[k]);
-        const int w = (int)threadIdx.x >> 6, row = ((int)threadIdx.x >> 4) & 3;
+        int tid = (int)threadIdx.x;
+        if constexpr (LEAN) asm volatile("" : "+v"(tid));
+        const int w = tid >> 6, row = (tid >> 4) & 3;
         if ((threadIdx.x & 15) == 0) {
             _Pragma("unroll") for (int k = 0; k < K2; k++) {
                 const int sub = (row & 1) * K2 + k, idx = (row >> 1) * K1 + sub;
@@ -495,7 +500,11 @@ __global__ __launch_bounds__(NL, WPS) void k_mpc_wave_group(const GroupEntry *__
                                                             const uint32_t *__restrict__ ord, int devcnt) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     using LD = impc::WaveLds<NL, VS, GS>;
-    GpuTeam<NL> wv{smem + LD::RED_OFF};
+    // (the denser instance of a shape: WaveQP's DENSE form of the iteration loop)
+    constexpr bool DENSE = WPS > Shape<VS>::WPS;
+    using TEAM = GpuTeam<NL, DENSE>;
+    using QP = impc::WaveQP<TEAM, NL, VS, GS, WF, TIER, DENSE>;
+    TEAM wv{smem + LD::RED_OFF};
     __shared__ unsigned next;
     int cur = -1;
     if (devcnt) {  // device-side active counts: the queue's length is their sum (ord puts them first)
@@ -517,10 +526,10 @@ __global__ __launch_bounds__(NL, WPS) void k_mpc_wave_group(const GroupEntry *__
         int e = 0;
         while (e + 1 < count && (int64_t)b >= g[e + 1].first) e++;
         if (e != cur) {
-            impc::WaveQP<GpuTeam<NL>, NL, VS, GS, WF, TIER>::load_tables(wv, g[e].T, smem);
+            QP::load_tables(wv, g[e].T, smem);
             cur = e;
         }
-        impc::WaveQP<GpuTeam<NL>, NL, VS, GS, WF, TIER> qp(wv, g[e].T, g[e].io, g[e].st, smem);
+        QP qp(wv, g[e].T, g[e].io, g[e].st, smem);
         qp.solve((int64_t)b - g[e].first);
     }
 }
@@ -1117,10 +1126,11 @@ int structured_solve(impc_batch b, hipStream_t st) {
 }
 
 // The instances built at the denser occupancy: the default horizon's two-tier one (the bench's),
-// whose iteration loop at 168 VGPRs reloads 7 values from scratch, none inside the sweeps.  The
-// one-tier and runtime-horizon instances compile to 9-21 reloads per iteration at three waves per
-// SIMD (the runtime-horizon one-tier instance with two inside a sweep), above the 8 of the plain
-// launch-bound change, and stay at the plain occupancy (profiles/r08/isa_loops_dense_not_built.txt).
+// whose iteration loop at 168 VGPRs holds no scratch or scalar-memory load (mpc_wave.hpp WaveQP
+// DENSE; 7 reloads per iteration before that form, profiles/r10).  The one-tier and runtime-horizon
+// instances compiled to 9-21 reloads per iteration at three waves per SIMD in the plain form (the
+// runtime-horizon one-tier instance with two inside a sweep) and stay at the plain occupancy
+// (profiles/r08/isa_loops_dense_not_built.txt).
 constexpr bool dense_instance(int vs, int gs, int wf, bool tier) {
     return vs == kWaveVS && gs <= Shape<kWaveVS>::HI_GMAX && tier && wf != 0 &&
            wf == impc::WaveLds<256, kWaveVS, 2>::WSPEC;

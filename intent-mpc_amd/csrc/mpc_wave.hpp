@@ -223,8 +223,10 @@ enum {
 #define IMPC_SEC_START() ((void)0)
 #endif
 
-// team reduction scratch (WaveLds RED_OFF): values x wavefronts of one team reduction
+// team reduction scratch (WaveLds RED_OFF): values x wavefronts of one team reduction in its first
+// kRedUsed doubles; the last 8 hold the rho table of the three-teams-per-CU instance (WaveQP::kRhoTab)
 constexpr int kRedLen = 128;
+constexpr int kRedUsed = kRedLen - 8;
 
 // LDS doubles per wave for (VS, GS)
 template <int NL, int VS, int GS>
@@ -344,7 +346,13 @@ IMPC_WF int row_type(double l, double u) {  // set_rho_vec (auxil.h:34)
 // for any W read from the tables.
 // TIER: the batch uses the two-tier products layout (WaveLds, T1r = kProdTier1); a one-tier
 // batch (T1r = CG4) runs the TIER = false instance, whose gathers are the plain CG4-row loops.
-template <class WV, int NL, int VS, int GS, int WF = 0, bool TIER = false>
+// DENSE: the three-teams-per-CU instance (168 VGPRs per lane).  Its iteration loop is arranged so
+// that nothing in it comes from scratch or scalar memory: the rows' rho / 1/rho are read from a
+// six-entry LDS table by row type (kRhoTab) instead of held per row, the loop-invariant operands
+// are per-pass values (begin_pass), one general entry's addresses are formed at their uses (gpk)
+// and the projections are written out (clampz_raw).  The same operations on the same values as the
+// plain form, which every other instance keeps unchanged.
+template <class WV, int NL, int VS, int GS, int WF = 0, bool TIER = false, bool DENSE = false>
 struct WaveQP {
     using LD = WaveLds<NL, VS, GS>;
     static_assert(WF == 0 || WF == LD::WSPEC || WF == LD::WSPEC2, "WF is 0 or one of the shape's compiled horizons");
@@ -402,11 +410,85 @@ struct WaveQP {
 
     // team-uniform: R stays in scalar registers, and each row's rho / 1/rho is selected from it
     // by the row type where used instead of occupying 4 VGPRs per row slot
-    IMPC_WF void set_rho(double r) { R.set(wv.uniform(r)); }
-    IMPC_WF double rhob(int s) const { return R.of(bt[s]); }
-    IMPC_WF double rhoib(int s) const { return R.inv(bt[s]); }
-    IMPC_WF double rhog_(int s) const { return R.of(gt[s]); }
-    IMPC_WF double rhoig_(int s) const { return R.inv(gt[s]); }
+    // DENSE: the same six values also in LDS (kRhoTab + 1 + t: rho of row type t, + 4 + t: 1/rho),
+    // where the iteration reads them with its other LDS operands.  (The optimiser hoists the selects
+    // out of the ADMM loop: 12 VGPRs of the three-per-CU instance's 168.)  Every caller is team-wide
+    // code; the barrier orders the table against the reads of the factorisation that follows.
+    static constexpr int kRhoTab = LD::RED_OFF + kRedUsed;
+    IMPC_WF void set_rho(double r) {
+        R.set(wv.uniform(r));
+        if constexpr (DENSE) {
+            if (L == 0) {
+                double *t = lds + kRhoTab;
+                t[0] = R.r_loose, t[1] = R.r_ineq, t[2] = R.r_eq;
+                t[3] = R.i_loose, t[4] = R.i_ineq, t[5] = R.i_eq;
+            }
+            wv.lsync();
+        }
+    }
+    IMPC_WF double rho_of(int t) const {
+        if constexpr (DENSE) return lds[kRhoTab + 1 + t]; else return R.of(t);
+    }
+    IMPC_WF double rho_inv(int t) const {
+        if constexpr (DENSE) return lds[kRhoTab + 4 + t]; else return R.inv(t);
+    }
+    IMPC_WF double rhob(int s) const { return rho_of(bt[s]); }
+    IMPC_WF double rhoib(int s) const { return rho_inv(bt[s]); }
+    IMPC_WF double rhog_(int s) const { return rho_of(gt[s]); }
+    IMPC_WF double rhoig_(int s) const { return rho_inv(gt[s]); }
+
+    // DENSE: the loop-invariant per-lane operands of the iteration -- the projection bounds, q and the
+    // second products tier's geometry -- as values of their own for each pass of the iteration loop
+    // (begin_pass, once per check interval).  Held as the members above they live from the setup to
+    // the output; at 168 VGPRs the register allocator splits such a range around the sweeps and
+    // reloads it from scratch in front of each use, one exposed round trip per value and iteration
+    // (five bounds in the update phase, the tier address and the row length in the rhs gather).  A
+    // value that lives for the pass only, and is used in every iteration of it, keeps its register.
+    struct Pass {
+        double lb[VS], ub[VS], lg[GS], ug[GS], q[VS];
+        int hq[VS];  // products index of the lane's second-tier column, or -1
+        int hp;      // second-tier row length
+    } ps_;
+    IMPC_WF static void opaque(double &v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(v));
+#else
+        (void)v;
+#endif
+    }
+    IMPC_WF void begin_pass() {
+        if constexpr (DENSE) {
+            static_assert(!DENSE || (TIER && WF > 0), "the denser instance is the two-tier default horizon's");
+            auto own = [](double v) {
+                opaque(v);
+                return v;
+            };
+            _Pragma("unroll") for (int s = 0; s < VS; s++) {
+                ps_.lb[s] = own(lb[s]);
+                ps_.ub[s] = own(ub[s]);
+                ps_.q[s] = own(q[s]);
+                ps_.hq[s] = hid_[s] >= 0 ? LD::T1 * LD::stride(13 * (WF + 1) - 5) + hid_[s] : -1;
+                opaque(ps_.hq[s]);
+            }
+            _Pragma("unroll") for (int s = 0; s < GS; s++) {
+                ps_.lg[s] = own(lg[s]);
+                ps_.ug[s] = own(ug[s]);
+            }
+            ps_.hp = LD::hsp(T.HS);
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" : "+s"(ps_.hp));  // (team-uniform: stays in a scalar register)
+#endif
+        }
+    }
+    // packed (product slot << 16 | column) of general entry e of slot s as the iteration uses it.
+    // DENSE: the last entry's is opaque there, so its two LDS addresses are formed at their uses
+    // (6 VALU instructions) instead of held across the loop -- the registers that took the last
+    // reload, of one such address, out of the update phase.
+    IMPC_WF int gpk(int s, int e) const {
+        int g = gc[s][e];
+        if (DENSE && s == GS - 1 && e == 3) opaque(g);
+        return g;
+    }
 
     // ADMM deltas of the last iteration (termination checks only): LDS or registers
     // (LDS of the one-variable-per-lane shape: WaveLds::DLT_OFF's comment)
@@ -615,6 +697,22 @@ struct WaveQP {
                 for (int t = 0; t < C4 - LD::T1; t += 4)
                     s += (q[t * hp] + q[(t + 1) * hp]) + (q[(t + 2) * hp] + q[(t + 3) * hp]);
             }
+        }
+        return s;
+    }
+    // col_gather of the iteration loop in the DENSE instance: the same reads and sums from the
+    // pass's own copy of the second tier's geometry (begin_pass)
+    IMPC_WF double col_gather_pass(int v, int slot) {
+        static_assert(LD::T1 == 4, "one first-tier group");
+        const double *pb = pbuf() + v;
+        constexpr int sd = LD::stride(13 * (WF + 1) - 5);
+        double s = 0.0;
+        s += (pb[0] + pb[sd]) + (pb[2 * sd] + pb[3 * sd]);
+        if (ps_.hq[slot] >= 0) {
+            const int hp = ps_.hp;
+            const double *q = pbuf() + ps_.hq[slot];
+            for (int t = 0; t < c4_ - LD::T1; t += 4)
+                s += (q[t * hp] + q[(t + 1) * hp]) + (q[(t + 2) * hp] + q[(t + 3) * hp]);
         }
         return s;
     }
@@ -1525,7 +1623,7 @@ struct WaveQP {
         _Pragma("unroll") for (int s = 0; s < GS; s++) {
             // (an empty slot writes a zero product to the discard slot)
             double vv = rhog_(s) * z[s] - y[s];
-            _Pragma("unroll") for (int e = 0; e < 4; e++) pb[gdst(s, e)] = a[s][e] * vv;
+            _Pragma("unroll") for (int e = 0; e < 4; e++) pb[gpk(s, e) >> 16] = a[s][e] * vv;
         }
         wv.lsync();
     }
@@ -1541,9 +1639,9 @@ struct WaveQP {
             _Pragma("unroll") for (int s = 0; s < VS; s++) {
                 int v = NL * s + L;
                 double vb = rhob(s) * zb[s] - yb[s];
-                double r = sigma * x[s] - q[s];
+                double r = sigma * x[s] - (DENSE ? ps_.q[s] : q[s]);
                 r += ab[s] * vb;
-                r += col_gather(v, hid_[s]);
+                if constexpr (DENSE) r += col_gather_pass(v, s); else r += col_gather(v, hid_[s]);
                 rb[v] = r;
             }
             wv.lsync();
@@ -1650,6 +1748,20 @@ struct WaveQP {
     // project_z (auxil.h): min(max(v, l), u), as v_max_f64 / v_min_f64 -- the same value as the
     // reference's c_max / c_min except the sign of a zero when v equals a zero bound
     IMPC_WF static double clampz(double v, double l, double u) { return __builtin_fmin(__builtin_fmax(v, l), u); }
+    // The same two instructions written out (DENSE, device code): in front of each v_max_f64 /
+    // v_min_f64 the compiler canonicalises a bound it cannot see the origin of (v_max_f64 b, b, b --
+    // a bound defined outside the iteration's basic block, so six FP64 instructions per iteration
+    // of the two-slot shape); a bound is never a NaN (load() clamps it), so that is the identity
+    IMPC_WF static double clampz_raw(double v, double l, double u) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        double r;
+        asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(v), "v"(l));
+        asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(r), "v"(u));
+        return r;
+#else
+        return clampz(v, l, u);
+#endif
+    }
 
     // update_x and the box rows (update_z / project / update_y), the general rows, and the
     // products of the next rhs (the end of every ADMM iteration).  need_delta: the check-iteration
@@ -1665,7 +1777,9 @@ struct WaveQP {
             x[s] = xn;
             double zt = ab[s] * xt;
             double zr = alpha * zt + oma * zb[s];
-            double zn = clampz(zr + rhoib(s) * yb[s], lb[s], ub[s]);
+            double zn;
+            if constexpr (DENSE) zn = clampz_raw(zr + rhoib(s) * yb[s], ps_.lb[s], ps_.ub[s]);
+            else zn = clampz(zr + rhoib(s) * yb[s], lb[s], ub[s]);
             double dy = rhob(s) * (zr - zn);
             yb[s] += dy;
             if (need_delta) dyb(s) = dy;
@@ -1675,14 +1789,16 @@ struct WaveQP {
         // x exchange, its A values, bounds and iterates zero, so it computes zeros
         double xg[GS][4];
         _Pragma("unroll") for (int s = 0; s < GS; s++) {
-            _Pragma("unroll") for (int e = 0; e < 4; e++) xg[s][e] = xb[gcol(s, e)];
+            _Pragma("unroll") for (int e = 0; e < 4; e++) xg[s][e] = xb[gpk(s, e) & 0xFFFF];
         }
         IMPC_LOADS_FIRST(4 * GS, 8 * GS);
         _Pragma("unroll") for (int s = 0; s < GS; s++) {
             double zt = 0.0;
             _Pragma("unroll") for (int e = 0; e < 4; e++) zt += a[s][e] * xg[s][e];
             double zr = alpha * zt + oma * z[s];
-            double zn = clampz(zr + rhoig_(s) * y[s], lg[s], ug[s]);
+            double zn;
+            if constexpr (DENSE) zn = clampz_raw(zr + rhoig_(s) * y[s], ps_.lg[s], ps_.ug[s]);
+            else zn = clampz(zr + rhoig_(s) * y[s], lg[s], ug[s]);
             double dy = rhog_(s) * (zr - zn);
             y[s] += dy;
             if (need_delta) dyg(s) = dy;
@@ -2164,6 +2280,7 @@ struct WaveQP {
                 if (rho_int && rho_left < nxt) nxt = rho_left;
                 const bool ce = chk && chk_left == nxt, re = rho_int && rho_left == nxt;
                 const bool nd_last = ce || iter + nxt - 1 == max_iter || tlim;
+                begin_pass();
                 for (int t = 1;; t++) {
                     iterate(t == nxt ? nd_last : tlim);
                     if (tlim) {
