@@ -1279,44 +1279,54 @@ struct WaveQP {
     // 2 kSweepPre = 1/4: v / 4 = 2 (c / 8) - F (v / 4), exact, and the captured steps are scaled back
     // when they are stored after the sweep.  (Keeping F's sign and negating every other step's c
     // instead was measured: 182.4-182.7 ms per config-3 launch against 171.8-171.9 for this form
-    // and the parent's 184.0, profiles/r09/kernel_ab.txt.)  Capture and prefetch distance as on the
-    // lane grid; the per-lane offsets come from the opaque lane index here, not from outside the
-    // ADMM loop.
+    // and the parent's 184.0, profiles/r09/kernel_ab.txt.)  The per-lane offsets come from the opaque
+    // lane index here, not from outside the ADMM loop.
+    // Capture as on the lane grid, the select pair behind the step's own add: behind the next step's
+    // instruction, inside its wait states, it was measured slower, as was a read distance of three
+    // (profiles/r11/).  What the sweep does around its steps is kept short instead: (F, c) are read
+    // kSweepAhead steps ahead and only for steps that exist (no read past stage WC - 1 of F or stage
+    // WC of cb, none repeated), the first step kept in a capture register is a plain copy (the other
+    // lanes' content is overwritten by their own steps or never stored), and the stores after the
+    // last step have no divergent branch.
+    static constexpr int kSweepAhead = 2;
     template <int WC, bool FWD>
     IMPC_WF void sweep_mfma(const double *cb, double *ob) {
+        constexpr int PD = kSweepAhead;
+        static_assert(PD >= 1 && PD <= WC, "the (F, c) ring is filled from existing steps only");
         const double *Fm = lds + LD::F_OFF;
-        const int l = lane_o() & 63;
-        constexpr int k0 = FWD ? 0 : WC - 1, k1 = FWD ? 1 : (WC - 2 > 0 ? WC - 2 : 0);  // stages of steps 0, 1
-        const int fse = mfmap::a_slot(l, false, FWD, !(k0 & 1)), fso = mfmap::a_slot(l, true, FWD, !(k1 & 1));
-        const int oe = mfmap::out_idx(l, false), oo = mfmap::out_idx(l, true);
-        auto fst = [](int m) { const int k = FWD ? m : WC - 1 - m; return 64 * (k > 0 ? k : 0); };
-        auto cst = [](int m) { const int k = FWD ? m + 1 : WC - 1 - m; return 13 * (k > 0 ? k : 0); };
+        const int lo = lane_o(), l = lo & 63;
+        constexpr int k0 = FWD ? 0 : WC - 1, k1 = FWD ? 1 : WC - 2;  // stages of steps 0, 1
+        const int fs[2] = {mfmap::a_slot(l, false, FWD, !(k0 & 1)), mfmap::a_slot(l, true, FWD, !(k1 & 1))};
+        const int os[2] = {mfmap::out_idx(l, false), mfmap::out_idx(l, true)};
+        auto fst = [](int m) { return 64 * (FWD ? m : WC - 1 - m); };       // m < WC
+        auto cst = [](int m) { return 13 * (FWD ? m + 1 : WC - 1 - m); };   // m < WC
         double v = 2.0 * cb[13 * (FWD ? 0 : WC) + mfmap::in_idx(l, false)];  // (c / 8) (1/4) / (1/8)
-        // (F, c) of the next even / odd step, loaded two steps ahead (forward reads past the last
-        // stage stay inside the LDS buffers and are never used)
-        double fe = Fm[fst(0) + fse], ce = cb[cst(0) + oe], fo = Fm[fst(1) + fso], co = cb[cst(1) + oo];
+        double fq[PD], cq[PD];
+        _Pragma("unroll") for (int p = 0; p < PD; p++) fq[p] = Fm[fst(p) + fs[p & 1]], cq[p] = cb[cst(p) + os[p & 1]];
         double c0[CQ], c1[CQ];
-        _Pragma("unroll") for (int q = 0; q < CQ; q++) c0[q] = c1[q] = 0.0;
-        _Pragma("unroll") for (int m = 0; m < WC; m += 2) {
-            const double f0 = fe, e0 = ce;
-            fe = Fm[fst(m + 2) + fse];
-            ce = cb[cst(m + 2) + oe];
-            v = wv.template mfma_step<false>(f0, e0, v);
-            capk(c0[m >> 4], v, mfmap::keep_mask((m >> 1) & 7, false));
-            if (m + 1 < WC) {
-                const double f1 = fo, e1 = co;
-                fo = Fm[fst(m + 3) + fso];
-                co = cb[cst(m + 3) + oo];
-                v = wv.template mfma_step<true>(f1, e1, v);
-                capk(c1[m >> 4], v, mfmap::keep_mask((m >> 1) & 7, true));
+        _Pragma("unroll") for (int m = 0; m < WC; m++) {
+            const double f0 = fq[m % PD], e0 = cq[m % PD];
+            if (m + PD < WC) {
+                fq[m % PD] = Fm[fst(m + PD) + fs[(m + PD) & 1]];
+                cq[m % PD] = cb[cst(m + PD) + os[(m + PD) & 1]];
             }
+            v = (m & 1) ? wv.template mfma_step<true>(f0, e0, v) : wv.template mfma_step<false>(f0, e0, v);
+            double &c = (m & 1) ? c1[m >> 4] : c0[m >> 4];
+            if ((m & 14) == 0) c = v;  // the register's first step
+            else capk(c, v, mfmap::keep_mask((m >> 1) & 7, m & 1));
         }
+        _Pragma("unroll") for (int q = 0; q < CQ; q++) {  // registers no step of this WC reaches
+            if (16 * q >= WC) c0[q] = 0.0;
+            if (16 * q + 1 >= WC) c1[q] = 0.0;
+        }
+        // one lane per element stores, the others write their discard slot
         const int he = mfmap::other(l, false), ho = mfmap::other(l, true);
         constexpr double back = 1.0 / (2.0 * kSweepPre);
+        double *junk = lds + LD::JUNK_OFF + lo;
         _Pragma("unroll") for (int q = 0; q < CQ; q++) {
             const int m0 = 16 * q + 2 * he, m1 = 16 * q + 2 * ho + 1;
-            if (m0 < WC) ob[13 * (FWD ? m0 + 1 : WC - 1 - m0) + oe] = back * c0[q];
-            if (m1 < WC) ob[13 * (FWD ? m1 + 1 : WC - 1 - m1) + oo] = back * c1[q];
+            *(m0 < WC ? ob + 13 * (FWD ? m0 + 1 : WC - 1 - m0) + os[0] : junk) = back * c0[q];
+            *(m1 < WC ? ob + 13 * (FWD ? m1 + 1 : WC - 1 - m1) + os[1] : junk) = back * c1[q];
         }
     }
 #endif

@@ -3,7 +3,11 @@
 object (llvm-objdump --offloading into a temp dir, then -d), finds the instance's function, and
 lists every backward branch (a loop: target .. branch) with its instruction count and the scratch,
 global and LDS memory instructions inside it -- where the register spills land relative to the
-ADMM iteration loop.  Usage: python tools/isa_loops.py '<256, 3, 3, 1, 39' [lib.so] [min_len]"""
+ADMM iteration loop.  Usage: python tools/isa_loops.py [--sweep-steps] '<256, 3, 3, 1, 39' [lib.so] [min_len]
+--sweep-steps: for every step of the matrix-instruction stage sweeps (the v_mfma_f64_4x4x4 of the
+raised-priority regions) also print what stands between the instruction and the DPP moves that read its
+result, with the s_nop wait states among it, and what stands between the step's add and the next
+matrix instruction -- the instructions that are issued on the serial chain without belonging to it."""
 import os
 import re
 import shutil
@@ -12,10 +16,12 @@ import sys
 import tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin"
-want = sys.argv[1] if len(sys.argv) > 1 else "<256, 3, 3, 1, 39"
-lib = os.path.abspath(sys.argv[2] if len(sys.argv) > 2 else os.path.join(os.path.dirname(__file__), "..",
-                                                                         "intent-mpc_amd", "lib", "libimpc_qp.so"))
-min_len = int(sys.argv[3]) if len(sys.argv) > 3 else 200
+argv = [a for a in sys.argv[1:] if a != "--sweep-steps"]
+sweep_steps = "--sweep-steps" in sys.argv[1:]
+want = argv[0] if len(argv) > 0 else "<256, 3, 3, 1, 39"
+lib = os.path.abspath(argv[1] if len(argv) > 1 else os.path.join(os.path.dirname(__file__), "..",
+                                                                 "intent-mpc_amd", "lib", "libimpc_qp.so"))
+min_len = int(argv[2]) if len(argv) > 2 else 200
 tmp = tempfile.mkdtemp()
 try:
     src = os.path.join(tmp, os.path.basename(lib))
@@ -87,6 +93,32 @@ def kinds(lo, hi):
     return c
 
 
+def sweep_step_lines(text):
+    """Per step of a sweep (text: the region's instructions): the instructions between the matrix
+    instruction and the first DPP move, and between the add behind the moves and the next one."""
+    ops = [t.split()[0] for t in text]
+    mf = [i for i, o in enumerate(ops) if o.startswith("v_mfma_f64_4x4x4")]
+
+    def short(i):  # waits with their operand, everything else by mnemonic
+        return text[i] if ops[i].startswith(("s_nop", "s_waitcnt")) else ops[i]
+
+    out = []
+    for n, i in enumerate(mf):
+        end = mf[n + 1] if n + 1 < len(mf) else len(ops)
+        dpp = next((k for k in range(i + 1, end) if ops[k].startswith("v_mov_b32_dpp")), None)
+        add = None if dpp is None else next((k for k in range(dpp + 1, end) if ops[k].startswith("v_add_f64")), None)
+        if add is None:
+            out.append(f"  step {n:2d}: no DPP move and add behind the instruction")
+            continue
+        behind = [short(k) for k in range(i + 1, dpp)]
+        ws = sum(int(text[k].split()[1]) + 1 for k in range(i + 1, dpp) if ops[k] == "s_nop")
+        tail = [short(k) for k in range(add + 1, end)] if n + 1 < len(mf) else ["(last step)"]
+        out.append(f"  step {n:2d}: behind the instruction [{', '.join(behind)}] ({ws} s_nop wait states, "
+                   f"{len(behind) - sum(o.startswith('s_nop') for o in behind)} other); "
+                   f"add .. next instruction [{', '.join(tail)}]")
+    return out
+
+
 tot = kinds(0, len(ins) - 1)
 print("whole function:", tot)
 # the raised-priority regions (s_setprio N > 0 .. s_setprio 0: the serial stage sweeps): a register
@@ -102,6 +134,8 @@ for i, (a, t) in enumerate(ins):
         c = kinds(up, i)
         print(f"setprio {ins[up][0]:#x}..{a:#x} ({i - up + 1} instructions): scratch_ld {c['scratch_ld']} "
               f"scratch_st {c['scratch_st']} ds {c['ds']} valu {c['valu']}")
+        if sweep_steps:
+            print("\n".join(sweep_step_lines([t for _, t in ins[up:i + 1]])))
         prio.append((up, i))
         up = None
 # the ADMM iteration loop: the innermost loop around each raised-priority region

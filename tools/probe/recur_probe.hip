@@ -34,6 +34,24 @@
 //               row DPP move + add; the block numbering alternates between even and odd steps (see the
 //               mf_* maps) so that the sum lands where the next step's B wants it
 //      15 / 16  as 13 / 14 with the capture select written in C++ (inverse ballot of the constant mask)
+//      17 .. 30 the 4x4x4 step with its off-chain instructions moved (km's FORM 1 .. 7, forward / backward
+//               each); every form loads (F, c) only for steps that exist:
+//                 1  the capture selects of step m issued behind the MFMA of step m + 1, inside its wait
+//                    states: each select names the MFMA's result as a read-write operand it does not touch,
+//                    so it can stand neither in front of the MFMA nor behind the DPP moves, and the hazard
+//                    recognizer still counts the MFMA -> DPP wait states (selects included)
+//                 2  as 1 with (F, c) loaded three steps ahead
+//                 3  no capture: step m's v stored by all 64 lanes (the 8 holders of an element write the
+//                    same value to the same address) behind the MFMA of step m + 1; loads three ahead (as
+//                    compiled, the 19 results stay in 38 VGPRs and the stores follow the last step)
+//                 4  as 2 with the 16 capture masks in SGPRs from before the first sweep
+//                 5  as 2 with the select written in C++ (inverse ballot) between two empty asm statements
+//                    that name the MFMA's result: the selects are instructions the hazard recognizer counts
+//                 6  the capture behind the step's own add as in 13 / 14, but as one instruction: v_mov_b64 under
+//                    the keep mask in EXEC (s_mov_b64 exec around it in one asm statement; the sweeping wave
+//                    has all 64 lanes active, and an SALU write of EXEC needs no wait state before a VALU
+//                    instruction); loads two ahead
+//                 7  as 6 with loads three ahead
 //     and their difference from a long-double evaluation next to the lane grid's.
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -332,10 +350,23 @@ __device__ void capc(double &d, double r, u64 MSK) {
     d = __hiloint2double(hi, lo);
 }
 
+// capc's select, ordered behind the producer of `tie` and in front of its readers (tie is not touched)
+__device__ void capd(double &d, double r, u64 MSK, double &tie) {
+    int lo = __double2loint(d), hi = __double2hiint(d);
+    asm("v_cndmask_b32 %0, %0, %2, %3" : "+v"(lo), "+v"(tie) : "v"(__double2loint(r)), "s"(MSK));
+    asm("v_cndmask_b32 %0, %0, %2, %3" : "+v"(hi), "+v"(tie) : "v"(__double2hiint(r)), "s"(MSK));
+    d = __hiloint2double(hi, lo);
+}
+
+// the capture as one 64-bit move under the mask in EXEC (all 64 lanes are active around it)
+__device__ void capx(double &d, double r, u64 MSK) {
+    asm("s_mov_b64 exec, %2\n\tv_mov_b64 %0, %1\n\ts_mov_b64 exec, -1" : "+v"(d) : "v"(r), "s"(MSK));
+}
+
 // Modes 11 / 12: the lane grid as the kernel runs it (fma(-f, v, c / 8), 8-lane sums, constant-mask
 // capture, stores after the sweep), forward / backward.  Modes 13 / 14: the 4x4x4 form.  F, t from the
 // host (gF row-major F_k, gt stride 13), results of wave 0 to gout for the arithmetic check.
-template <int MODE>
+template <int MODE, int FORM = 0>
 __global__ void km(const double *gF, const double *gt, double *gout, double *o, u64 *cyc) {
     __shared__ double F[8][64 * (W + 3)];
     __shared__ double t[8][13 * (W + 4)], out[8][13 * (W + 4)];
@@ -352,10 +383,65 @@ __global__ void km(const double *gF, const double *gt, double *gout, double *o, 
     double *rb = out[wv];
     double acc = 0.0;
     u64 c0 = 0;
+    u64 mk[16];
+    if (FORM == 4) {
+        _Pragma("unroll") for (int q = 0; q < 16; q++) {
+            mk[q] = mf_mask(q & 7, q >> 3);
+            asm volatile("" : "+s"(mk[q]));
+        }
+    }
     for (int rep = -1; rep < REP; rep++) {
         if (rep == 0) c0 = __builtin_amdgcn_s_memtime();
         double ce[2] = {0, 0}, co[2] = {0, 0};
-        if (!MF) {
+        if (FORM > 0) {
+            constexpr int PD = (FORM == 1 || FORM == 6) ? 2 : 3;
+            const int fs[2] = {mf_fslot(l, false, FWD), mf_fslot(l, true, FWD)};
+            const int os[2] = {mf_out(l, false), mf_out(l, true)};
+            double a = (1.0 / kMfmaScale) * tb[(FWD ? 0 : 13 * W) + mf_in(l, false)];
+            auto fk = [](int m) { return 64 * (FWD ? m : W - 1 - m); };
+            auto tk = [](int m) { return 13 * (FWD ? m + 1 : W - 1 - m); };
+            double fq[PD], tq[PD];
+            _Pragma("unroll") for (int p = 0; p < PD; p++) fq[p] = Fm[fk(p) + fs[p & 1]], tq[p] = tb[tk(p) + os[p & 1]];
+            _Pragma("unroll") for (int m = 0; m < W; m++) {
+                const double f0 = fq[m % PD], t0 = tq[m % PD];
+                if (m + PD < W) fq[m % PD] = Fm[fk(m + PD) + fs[(m + PD) & 1]], tq[m % PD] = tb[tk(m + PD) + os[(m + PD) & 1]];
+                double d = mfma4(f0, a, t0);
+                if (FORM >= 6) {
+                    a = (m & 1) ? d + dpp<0x128, true>(d) : d + dpp<0x141, true>(d);
+                    if (m + 1 < W) capx((m & 1) ? co[m >> 4] : ce[m >> 4], a, mf_mask((m >> 1) & 7, m & 1));
+                    continue;
+                }
+                if (m > 0) {  // step m - 1, whose v is still in a
+                    const int n = m - 1;
+                    if (FORM == 3) {
+                        rb[tk(n) + os[n & 1]] = a;
+                    } else if (FORM == 5) {
+                        double &cd = (n & 1) ? co[n >> 4] : ce[n >> 4];
+                        asm("" : "+v"(a), "+v"(d));
+                        capc<true>(cd, a, mf_mask((n >> 1) & 7, n & 1));
+                        asm("" : "+v"(cd), "+v"(d));
+                    } else capd((n & 1) ? co[n >> 4] : ce[n >> 4], a, FORM == 4 ? mk[((n >> 1) & 7) + 8 * (n & 1)] : mf_mask((n >> 1) & 7, n & 1), d);
+                }
+                a = (m & 1) ? d + dpp<0x128, true>(d) : d + dpp<0x141, true>(d);
+                if (FORM == 5) {  // the step's order: MFMA, selects, LDS reads, DPP moves and add
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
+                }
+            }
+            if (FORM == 3) {
+                rb[tk(W - 1) + os[(W - 1) & 1]] = a;
+            } else {
+                capc(((W - 1) & 1) ? co[(W - 1) >> 4] : ce[(W - 1) >> 4], a, mf_mask(((W - 1) >> 1) & 7, (W - 1) & 1));
+                _Pragma("unroll") for (int q = 0; q < 2; q++) {
+                    const int m0 = 16 * q + 2 * mf_other(l, false), m1 = 16 * q + 2 * mf_other(l, true) + 1;
+                    if (m0 < W) rb[tk(m0) + os[0]] = ce[q];
+                    if (m1 < W) rb[tk(m1) + os[1]] = co[q];
+                }
+            }
+            acc += a;
+        } else if (!MF) {
             // even steps m: strided sum when the stage k is even (forward k = m, backward k = W-1-m)
             constexpr bool S0 = FWD ? true : ((W - 1) & 1) == 0 ? false : true;  // bwd: odd k strided
             const int i0 = S0 ? i : j, j0 = S0 ? j : i;                         // even step: in at i0, out at j0
@@ -419,7 +505,7 @@ __global__ void km(const double *gF, const double *gt, double *gout, double *o, 
     }
     const u64 c1 = __builtin_amdgcn_s_memtime();
     o[threadIdx.x] = acc;
-    if (threadIdx.x == 0) cyc[MODE] = (c1 - c0) * 10 / (REP * W);
+    if (threadIdx.x == 0) cyc[FORM ? 15 + 2 * FORM + !FWD : MODE] = (c1 - c0) * 10 / (REP * W);
     if (wv == 0)
         for (int p = l; p < 13 * (W + 4); p += 64) gout[p] = rb[p];
 }
@@ -457,7 +543,7 @@ static void host_sweep(const double *gF, const double *gt, bool fwd, long double
 
 static int mfma4_modes(double *o) {
     // operand layout
-    u64 *dm, *dc, hm[4096], hc[20] = {};
+    u64 *dm, *dc, hm[4096], hc[32] = {};
     if (hipMalloc(&dm, sizeof(hm)) || hipMalloc(&dc, sizeof(hc))) return 1;
     hipLaunchKernelGGL(k_layout, 1, 64, 0, 0, dm);
     if (hipMemcpy(hm, dm, sizeof(hm), hipMemcpyDeviceToHost)) return 1;
@@ -493,7 +579,8 @@ static int mfma4_modes(double *o) {
     for (int v = 0; v < 4; v++) printf("%-28s %5.1f\n", ln[v], hc[v] / 10.0);
     // the sweeps
     constexpr int NF = 64 * (W + 3), NT = 13 * (W + 4);
-    static double gF[NF], gt[NT], ho[6][NT];
+    constexpr int NM = 20;
+    static double gF[NF], gt[NT], ho[NM][NT];
     static long double ref[2][3][NT];
     u64 s = 0x9E3779B97F4A7C15ull;
     auto rnd = [&]() { s = s * 6364136223846793005ull + 1442695040888963407ull; return (double)(s >> 11) / 9007199254740992.0 - 0.5; };
@@ -508,26 +595,51 @@ static int mfma4_modes(double *o) {
         host_sweep<2>(gF, gt, d == 0, ref[d][2]);
     }
     const char *mn[] = {"grid, kernel form, forward", "grid, kernel form, backward", "mfma 4x4x4, forward", "mfma 4x4x4, backward",
-                        "mfma 4x4x4, C++ select, fwd", "mfma 4x4x4, C++ select, bwd"};
+                        "mfma 4x4x4, C++ select, fwd", "mfma 4x4x4, C++ select, bwd",
+                        "1 select behind next MFMA, f", "1 select behind next MFMA, b",
+                        "2 as 1, loads 3 ahead, fwd", "2 as 1, loads 3 ahead, bwd",
+                        "3 store per step, no capt, f", "3 store per step, no capt, b",
+                        "4 as 2, masks stay in SGPRs,f", "4 as 2, masks stay in SGPRs,b",
+                        "5 as 2, C++ select fenced, f", "5 as 2, C++ select fenced, b",
+                        "6 one mov under EXEC mask, f", "6 one mov under EXEC mask, b",
+                        "7 as 6, loads 3 ahead, fwd", "7 as 6, loads 3 ahead, bwd"};
     for (int threads : {64, 512}) {
-        for (int it = 0; it < 2; it++)
-            for (int m = 0; m < 6; m++) {
+        u64 hp[32] = {};  // the first of the two repeats
+        for (int it = 0; it < 2; it++) {
+            if (it == 1 && hipMemcpy(hp, dc, sizeof(hp), hipMemcpyDeviceToHost)) return 1;
+            for (int m = 0; m < NM; m++) {
                 if (m == 0) hipLaunchKernelGGL(km<11>, 1, threads, 0, 0, dF, dt, dout, o, dc);
                 if (m == 1) hipLaunchKernelGGL(km<12>, 1, threads, 0, 0, dF, dt, dout, o, dc);
                 if (m == 2) hipLaunchKernelGGL(km<13>, 1, threads, 0, 0, dF, dt, dout, o, dc);
                 if (m == 3) hipLaunchKernelGGL(km<14>, 1, threads, 0, 0, dF, dt, dout, o, dc);
                 if (m == 4) hipLaunchKernelGGL(km<15>, 1, threads, 0, 0, dF, dt, dout, o, dc);
                 if (m == 5) hipLaunchKernelGGL(km<16>, 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 6) hipLaunchKernelGGL((km<13, 1>), 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 7) hipLaunchKernelGGL((km<14, 1>), 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 8) hipLaunchKernelGGL((km<13, 2>), 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 9) hipLaunchKernelGGL((km<14, 2>), 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 10) hipLaunchKernelGGL((km<13, 3>), 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 11) hipLaunchKernelGGL((km<14, 3>), 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 12) hipLaunchKernelGGL((km<13, 4>), 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 13) hipLaunchKernelGGL((km<14, 4>), 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 14) hipLaunchKernelGGL((km<13, 5>), 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 15) hipLaunchKernelGGL((km<14, 5>), 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 16) hipLaunchKernelGGL((km<13, 6>), 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 17) hipLaunchKernelGGL((km<14, 6>), 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 18) hipLaunchKernelGGL((km<13, 7>), 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 19) hipLaunchKernelGGL((km<14, 7>), 1, threads, 0, 0, dF, dt, dout, o, dc);
                 if (hipMemcpy(ho[m], dout, sizeof(gt), hipMemcpyDeviceToHost)) return 1;
             }
+        }
         if (hipMemcpy(hc, dc, sizeof(hc), hipMemcpyDeviceToHost)) return 1;
         printf("-- %d lanes (%d wave(s) per SIMD), capture included\n", threads, threads > 256 ? 2 : 1);
-        for (int m = 0; m < 6; m++)
-            printf("%-28s %5.1f cyc/step  (%.3f x the grid)\n", mn[m], hc[11 + m] / 10.0, (double)hc[11 + m] / hc[11 + (m & 1)]);
+        for (int m = 0; m < NM; m++)
+            printf("%-30s %5.1f cyc/step  (%.3f x the grid, %.3f x the 4x4x4 kernel form; repeat before it %5.1f)\n", mn[m],
+                   hc[11 + m] / 10.0, (double)hc[11 + m] / hc[11 + (m & 1)], (double)hc[11 + m] / hc[13 + (m & 1)], hp[11 + m] / 10.0);
     }
     // arithmetic (wave 0 of the last run): max |v - long double| / max |long double| over all stages
     printf("-- arithmetic, W = %d steps on random F, t\n", W);
-    for (int m = 0; m < 6; m++) {
+    for (int m = 0; m < NM; m++) {
         const int d = m & 1, s0 = d == 0 ? 1 : 0;
         long double mx = 0, df = 0;
         int nb[3] = {0, 0, 0};
@@ -538,7 +650,7 @@ static int mfma4_modes(double *o) {
                 df = fmaxl(df, fabsl(ho[m][p] - ref[d][0][p]));
                 for (int q = 1; q < 3; q++) nb[q] += ho[m][p] != (double)ref[d][q][p];
             }
-        printf("%-28s rel diff from long double %.3Le", mn[m], df / mx);
+        printf("%-30s rel diff from long double %.3Le", mn[m], df / mx);
         if (m >= 2) printf("; of %d values %d differ from the k-ascending fma chain, %d from k-descending", 8 * W, nb[1], nb[2]);
         printf("\n");
     }
