@@ -36,12 +36,13 @@ SHIMT   := $(HARNDIR)/shim_test
 REPLANX := $(HARNDIR)/replan_example
 DETECTH := $(HARNDIR)/libdetect_harness.so
 MFMODEL := $(HARNDIR)/sweep_mfma_model
+STMODEL := $(HARNDIR)/sweep_store_model
 
 .PHONY: all lib oracle harness prof variant clean
 all: lib oracle harness
 lib: $(LIB)
 oracle: $(ORACLE)
-harness: $(HARNESS) $(EMU) $(EMU64) $(SHIMT) $(REPLANX) $(DETECTH) $(MFMODEL)
+harness: $(HARNESS) $(EMU) $(EMU64) $(SHIMT) $(REPLANX) $(DETECTH) $(MFMODEL) $(STMODEL)
 
 $(LIBDIR)/impc_qp.o: $(CSRC)/impc_qp.hip $(CSRC)/admm_core.hpp $(CSRC)/symbolic.hpp $(CSRC)/mpc_wave.hpp \
 		$(CSRC)/mpc_structure.hpp $(CSRC)/select.hpp $(CSRC)/mpc_build.hpp $(CSRC)/mpc_qp_internal.hpp \
@@ -133,6 +134,11 @@ $(DETECTH): $(ROOT)/tests/native/detect_harness.cpp $(CSRC)/detect_gate.hpp
 # host model of the stage recursions on the FP64 matrix instruction against a plain loop (stand-alone,
 # host only; SAN="-fsanitize=address,undefined" for a checked build)
 $(MFMODEL): $(ROOT)/tests/native/sweep_mfma_model.cpp $(CSRC)/sweep_mfma_map.hpp
+	@mkdir -p $(HARNDIR)
+	$(CXX) -O1 -g -std=c++17 -Wall -ffp-contract=off $(SAN) $< -o $@
+
+# host model of the sweeps' capture registers and their early stores (stand-alone, host only; SAN as above)
+$(STMODEL): $(ROOT)/tests/native/sweep_store_model.cpp $(CSRC)/sweep_mfma_map.hpp
 	@mkdir -p $(HARNDIR)
 	$(CXX) -O1 -g -std=c++17 -Wall -ffp-contract=off $(SAN) $< -o $@
 

@@ -78,6 +78,20 @@ namespace impc {
 #else
 #define IMPC_SWEEP_MFMA_DEV 0
 #endif
+// What the default horizon's matrix-instruction sweeps do around their steps (round 12; 0: the
+// round-11 form, A/B variants only; profiles/r12/kernel_ab.txt):
+// IMPC_SWEEP_PRO: the sweeping wavefront forms its lane maps and store addresses and issues its
+// first F reads in front of the barrier that releases the sweep (config 3: 145.7-146.3 -> 143.9-144.0
+// ms per launch)
+// IMPC_SWEEP_EARLY: a capture register is scaled back and stored behind its last step (with the
+// prologue: -> 142.2-142.4 ms; without it the store addresses are formed between the steps and it
+// measured slower than the parent, 147.3-147.4)
+#ifndef IMPC_SWEEP_PRO
+#define IMPC_SWEEP_PRO 1
+#endif
+#ifndef IMPC_SWEEP_EARLY
+#define IMPC_SWEEP_EARLY 1
+#endif
 #ifndef IMPC_DUP
 #define IMPC_DUP -1
 #endif
@@ -1262,6 +1276,12 @@ struct WaveQP {
         }
     }
 
+    // The round-12 forms are for the default horizon's sweep (W = 19) in device code: the long
+    // shape's runtime-W instance keeps its W = 39 sweep as it was.
+    static constexpr bool kSweep19 = IMPC_SWEEP_MFMA_DEV && !CHUNK && LD::WSPEC == 19;
+    static constexpr bool kSweepPro = kSweep19 && IMPC_SWEEP_PRO != 0;
+    static constexpr bool kSweepEarly = kSweepPro && IMPC_SWEEP_EARLY != 0;
+
 #if IMPC_SWEEP_MFMA_DEV
     // The select of capm by a lane mask given as a constant (mfmap::keep_mask)
     IMPC_WF static void capk(double &d, double r, uint64_t msk) {
@@ -1277,7 +1297,7 @@ struct WaveQP {
     // running vector, C the input c), one DPP move of the partner block's D and one add.  cb holds
     // c * kSweepPre = c / 8 and both blocks of a row add it, so the chain runs in units of
     // 2 kSweepPre = 1/4: v / 4 = 2 (c / 8) - F (v / 4), exact, and the captured steps are scaled back
-    // when they are stored after the sweep.  (Keeping F's sign and negating every other step's c
+    // when they are stored (sweep_run).  (Keeping F's sign and negating every other step's c
     // instead was measured: 182.4-182.7 ms per config-3 launch against 171.8-171.9 for this form
     // and the parent's 184.0, profiles/r09/kernel_ab.txt.)  The per-lane offsets come from the opaque
     // lane index here, not from outside the ADMM loop.
@@ -1327,6 +1347,81 @@ struct WaveQP {
             const int m0 = 16 * q + 2 * he, m1 = 16 * q + 2 * ho + 1;
             *(m0 < WC ? ob + 13 * (FWD ? m0 + 1 : WC - 1 - m0) + os[0] : junk) = back * c0[q];
             *(m1 < WC ? ob + 13 * (FWD ? m1 + 1 : WC - 1 - m1) + os[1] : junk) = back * c1[q];
+        }
+    }
+    // The default horizon's sweep in two parts (kSweepPro; the same reads, steps, values and stores as
+    // sweep_mfma).  sweep_pro is what depends on neither cb's nor ob's content: the lane's F slots and
+    // c indices by step parity, its element of the start vector, where it stores capture register q of
+    // the even (s0) / odd (s1) steps -- the element it owns or its discard slot -- and the first
+    // kSweepAhead F reads (F is constant across an iteration; factorize() rewrites it behind barriers
+    // of its own).  iterate() has the sweeping wavefront form it in front of the barrier that releases
+    // the sweep, where the other wavefronts' arrival covers it; from the opaque lane index inside the
+    // iteration, as before.
+    struct SweepPro {
+        int lo, fs[2], os[2], in;
+        double *s0[CQ], *s1[CQ];
+        double fq[kSweepAhead];
+    };
+    template <int WC, bool FWD>
+    IMPC_WF void sweep_stores(SweepPro &p, double *ob) {
+        // one lane per element stores, the others write their discard slot
+        const int l = p.lo & 63, he = mfmap::other(l, false), ho = mfmap::other(l, true);
+        double *junk = lds + LD::JUNK_OFF + p.lo;
+        _Pragma("unroll") for (int q = 0; q < CQ; q++) {
+            const int m0 = mfmap::cap_step(q, false, he), m1 = mfmap::cap_step(q, true, ho);
+            p.s0[q] = m0 < WC ? ob + 13 * (FWD ? m0 + 1 : WC - 1 - m0) + p.os[0] : junk;
+            p.s1[q] = m1 < WC ? ob + 13 * (FWD ? m1 + 1 : WC - 1 - m1) + p.os[1] : junk;
+        }
+    }
+    template <int WC, bool FWD>
+    IMPC_WF void sweep_pro(SweepPro &p, double *ob) {
+        const double *Fm = lds + LD::F_OFF;
+        p.lo = lane_o();
+        const int l = p.lo & 63;
+        constexpr int k0 = FWD ? 0 : WC - 1, k1 = FWD ? 1 : WC - 2;  // stages of steps 0, 1
+        p.fs[0] = mfmap::a_slot(l, false, FWD, !(k0 & 1)), p.fs[1] = mfmap::a_slot(l, true, FWD, !(k1 & 1));
+        p.os[0] = mfmap::out_idx(l, false), p.os[1] = mfmap::out_idx(l, true);
+        p.in = mfmap::in_idx(l, false);
+        _Pragma("unroll") for (int q = 0; q < kSweepAhead; q++)
+            p.fq[q] = Fm[64 * (FWD ? q : WC - 1 - q) + p.fs[q & 1]];
+        sweep_stores<WC, FWD>(p, ob);
+    }
+    // The steps behind the barrier.  kSweepEarly: each capture register is scaled back and stored
+    // behind the last step that writes it (mfmap::cap_final: c0[0] / c1[0] go out during steps 15-18),
+    // so only the last steps' registers are left when the sweep ends.
+    template <int WC, bool FWD>
+    IMPC_WF void sweep_run(const SweepPro &p, const double *cb) {
+        constexpr int PD = kSweepAhead;
+        static_assert(PD >= 1 && PD <= WC, "the (F, c) ring is filled from existing steps only");
+        const double *Fm = lds + LD::F_OFF;
+        auto fst = [](int m) { return 64 * (FWD ? m : WC - 1 - m); };       // m < WC
+        auto cst = [](int m) { return 13 * (FWD ? m + 1 : WC - 1 - m); };   // m < WC
+        constexpr double back = 1.0 / (2.0 * kSweepPre);
+        double v = 2.0 * cb[13 * (FWD ? 0 : WC) + p.in];  // (c / 8) (1/4) / (1/8)
+        double fq[PD], cq[PD];
+        _Pragma("unroll") for (int q = 0; q < PD; q++) fq[q] = p.fq[q], cq[q] = cb[cst(q) + p.os[q & 1]];
+        double c0[CQ], c1[CQ];
+        _Pragma("unroll") for (int m = 0; m < WC; m++) {
+            const double f0 = fq[m % PD], e0 = cq[m % PD];
+            if (m + PD < WC) {
+                fq[m % PD] = Fm[fst(m + PD) + p.fs[(m + PD) & 1]];
+                cq[m % PD] = cb[cst(m + PD) + p.os[(m + PD) & 1]];
+            }
+            v = (m & 1) ? wv.template mfma_step<true>(f0, e0, v) : wv.template mfma_step<false>(f0, e0, v);
+            double &c = (m & 1) ? c1[m >> 4] : c0[m >> 4];
+            if ((m & 14) == 0) c = v;  // the register's first step
+            else capk(c, v, mfmap::keep_mask((m >> 1) & 7, m & 1));
+            if constexpr (kSweepEarly) {
+                if (m == mfmap::cap_final(WC, m >> 4, m & 1)) *((m & 1) ? p.s1[m >> 4] : p.s0[m >> 4]) = back * c;
+            }
+        }
+        _Pragma("unroll") for (int q = 0; q < CQ; q++) {  // registers no step of this WC reaches
+            if (16 * q >= WC) c0[q] = 0.0;
+            if (16 * q + 1 >= WC) c1[q] = 0.0;
+        }
+        _Pragma("unroll") for (int q = 0; q < CQ; q++) {
+            if (!kSweepEarly || mfmap::cap_final(WC, q, false) < 0) *p.s0[q] = back * c0[q];
+            if (!kSweepEarly || mfmap::cap_final(WC, q, true) < 0) *p.s1[q] = back * c1[q];
         }
     }
 #endif
@@ -1643,6 +1738,11 @@ struct WaveQP {
         const int W = Wst();
         double *rb = rbuf(), *tb = tbuf(), *eb = ebuf(), *xb = xbuf();
         const double sigma = sig_;
+        const bool sweeper = (L >> 6) == rw;
+#if IMPC_SWEEP_MFMA_DEV
+        // kSweepPro: each sweep's prologue, formed by its wavefront in front of the releasing barrier
+        [[maybe_unused]] SweepPro fpro, bpro;
+#endif
         IMPC_REP(kSecRhs) {
             // rhs = sigma x - q + A' v   (stage order; an empty slot's iterates, bounds and column
             // are zero, so it writes 0)
@@ -1673,6 +1773,13 @@ struct WaveQP {
                 _Pragma("unroll") for (int cc = 0; cc < 5; cc++) t -= cp[s][cc] * rv[cc];
                 tb[v] = kSweepPre * t;  // the forward sweep's input, pre-scaled (rstep)
             }
+#if IMPC_SWEEP_MFMA_DEV
+            if constexpr (kSweepPro) {
+                if (sweeper && W == LD::WSPEC) {
+                    sweep_pro<LD::WSPEC, true>(fpro, rb);
+                }
+            }
+#endif
             wv.lsync();
         }
         IMPC_SEC(kSecS1);
@@ -1690,11 +1797,14 @@ struct WaveQP {
                 fwd_chunked5(tb, rb);
             } else if constexpr (CHUNK) {
                 fwd_chunked(tb, rb);
-            } else if ((L >> 6) == rw) {
+            } else if (sweeper) {
                 IMPC_PRIO_UP();
-                if (W == LD::WSPEC)
+                if (W == LD::WSPEC) {
+#if IMPC_SWEEP_MFMA_DEV
+                    if constexpr (kSweepPro) sweep_run<LD::WSPEC, true>(fpro, tb); else
+#endif
                     fwd_sweep<LD::WSPEC>(tb, rb, W);
-                else
+                } else
                     fwd_sweep<0>(tb, rb, W);
                 IMPC_PRIO_DOWN();
             }
@@ -1713,6 +1823,13 @@ struct WaveQP {
                 // the state part pre-scaled for the backward sweep (rstep); S5 reads the controls' e
                 eb[NL * s + L] = vr_[s] < 8 ? kSweepPre * e : e;
             }
+#if IMPC_SWEEP_MFMA_DEV
+            if constexpr (kSweepPro) {
+                if (sweeper && W == LD::WSPEC) {
+                    sweep_pro<LD::WSPEC, false>(bpro, xb);
+                }
+            }
+#endif
             wv.lsync();
         }
         IMPC_SEC(kSecS3);
@@ -1724,11 +1841,14 @@ struct WaveQP {
                 bwd_chunked5(eb, xb);
             } else if constexpr (CHUNK) {
                 bwd_chunked(eb, xb);
-            } else if ((L >> 6) == rw) {
+            } else if (sweeper) {
                 IMPC_PRIO_UP();
-                if (W == LD::WSPEC)
+                if (W == LD::WSPEC) {
+#if IMPC_SWEEP_MFMA_DEV
+                    if constexpr (kSweepPro) sweep_run<LD::WSPEC, false>(bpro, eb); else
+#endif
                     bwd_sweep<((LD::WSPEC - 1) & 1) != 0, LD::WSPEC>(eb, xb, W);
-                else if ((W - 1) & 1)
+                } else if ((W - 1) & 1)
                     bwd_sweep<true, 0>(eb, xb, W);
                 else
                     bwd_sweep<false, 0>(eb, xb, W);

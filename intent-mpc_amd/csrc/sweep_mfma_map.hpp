@@ -45,6 +45,17 @@ constexpr int other(int l, bool odd) { return lx(l) + 4 * bcol(l, odd); }
 constexpr uint64_t keep_mask(int v, bool odd) {
     return odd ? 0x0001000100010001ull * (0x11ull << ((v & 3) + 8 * (v >> 2))) : 0x0101010101010101ull << v;
 }
+// Capture registers of an unrolled sweep of wc steps: step m is kept in register m >> 4 of the even-
+// (c0) or odd-step (c1) array, by the lane whose `other` index is (m / 2) % 8.
+// cap_step: the step that lane keeps in register q; it exists when it is below wc.
+constexpr int cap_step(int q, bool odd, int oth) { return 16 * q + 2 * oth + (odd ? 1 : 0); }
+// cap_final: the last step of the sweep that writes register q (-1: none does).  After it the
+// register is final in every lane and can be stored while the later steps run.
+constexpr int cap_final(int wc, int q, bool odd) {
+    const int first = 16 * q + (odd ? 1 : 0), top = first + 14;  // the register's steps: first, first + 2, .. top
+    if (first >= wc) return -1;
+    return top < wc ? top : wc - 1 - ((wc - 1 - first) & 1);
+}
 // partner lane of the pair sum
 constexpr int partner(int l, bool odd) { return odd ? l ^ 8 : (l & ~7) | (7 - (l & 7)); }
 

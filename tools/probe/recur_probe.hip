@@ -52,6 +52,10 @@
 //                    has all 64 lanes active, and an SALU write of EXEC needs no wait state before a VALU
 //                    instruction); loads two ahead
 //                 7  as 6 with loads three ahead
+//                 8  no capture registers, keep masks or stores after the sweep: every step's v', times the
+//                    scale-back factor (an opaque 1.0 here), stored by all 64 lanes behind the step's own add,
+//                    where the select pair sits in 13 / 14 (the 8 holders of an element write the same value);
+//                    a compiler memory fence behind each store keeps them one per step; loads two ahead
 //     and their difference from a long-double evaluation next to the lane grid's.
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -390,11 +394,13 @@ __global__ void km(const double *gF, const double *gt, double *gout, double *o, 
             asm volatile("" : "+s"(mk[q]));
         }
     }
+    double back = 1.0;  // FORM 8: the kernel's scale-back multiply, by a factor the compiler cannot fold
+    asm volatile("" : "+v"(back));
     for (int rep = -1; rep < REP; rep++) {
         if (rep == 0) c0 = __builtin_amdgcn_s_memtime();
         double ce[2] = {0, 0}, co[2] = {0, 0};
         if (FORM > 0) {
-            constexpr int PD = (FORM == 1 || FORM == 6) ? 2 : 3;
+            constexpr int PD = (FORM == 1 || FORM == 6 || FORM == 8) ? 2 : 3;
             const int fs[2] = {mf_fslot(l, false, FWD), mf_fslot(l, true, FWD)};
             const int os[2] = {mf_out(l, false), mf_out(l, true)};
             double a = (1.0 / kMfmaScale) * tb[(FWD ? 0 : 13 * W) + mf_in(l, false)];
@@ -406,6 +412,12 @@ __global__ void km(const double *gF, const double *gt, double *gout, double *o, 
                 const double f0 = fq[m % PD], t0 = tq[m % PD];
                 if (m + PD < W) fq[m % PD] = Fm[fk(m + PD) + fs[(m + PD) & 1]], tq[m % PD] = tb[tk(m + PD) + os[(m + PD) & 1]];
                 double d = mfma4(f0, a, t0);
+                if (FORM == 8) {
+                    a = (m & 1) ? d + dpp<0x128, true>(d) : d + dpp<0x141, true>(d);
+                    rb[tk(m) + os[m & 1]] = back * a;
+                    asm volatile("" ::: "memory");  // the store is issued here, not collected behind the sweep
+                    continue;
+                }
                 if (FORM >= 6) {
                     a = (m & 1) ? d + dpp<0x128, true>(d) : d + dpp<0x141, true>(d);
                     if (m + 1 < W) capx((m & 1) ? co[m >> 4] : ce[m >> 4], a, mf_mask((m >> 1) & 7, m & 1));
@@ -430,7 +442,8 @@ __global__ void km(const double *gF, const double *gt, double *gout, double *o, 
                     __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
                 }
             }
-            if (FORM == 3) {
+            if (FORM == 8) {
+            } else if (FORM == 3) {
                 rb[tk(W - 1) + os[(W - 1) & 1]] = a;
             } else {
                 capc(((W - 1) & 1) ? co[(W - 1) >> 4] : ce[(W - 1) >> 4], a, mf_mask(((W - 1) >> 1) & 7, (W - 1) & 1));
@@ -543,7 +556,7 @@ static void host_sweep(const double *gF, const double *gt, bool fwd, long double
 
 static int mfma4_modes(double *o) {
     // operand layout
-    u64 *dm, *dc, hm[4096], hc[32] = {};
+    u64 *dm, *dc, hm[4096], hc[36] = {};
     if (hipMalloc(&dm, sizeof(hm)) || hipMalloc(&dc, sizeof(hc))) return 1;
     hipLaunchKernelGGL(k_layout, 1, 64, 0, 0, dm);
     if (hipMemcpy(hm, dm, sizeof(hm), hipMemcpyDeviceToHost)) return 1;
@@ -579,7 +592,7 @@ static int mfma4_modes(double *o) {
     for (int v = 0; v < 4; v++) printf("%-28s %5.1f\n", ln[v], hc[v] / 10.0);
     // the sweeps
     constexpr int NF = 64 * (W + 3), NT = 13 * (W + 4);
-    constexpr int NM = 20;
+    constexpr int NM = 22;
     static double gF[NF], gt[NT], ho[NM][NT];
     static long double ref[2][3][NT];
     u64 s = 0x9E3779B97F4A7C15ull;
@@ -602,9 +615,10 @@ static int mfma4_modes(double *o) {
                         "4 as 2, masks stay in SGPRs,f", "4 as 2, masks stay in SGPRs,b",
                         "5 as 2, C++ select fenced, f", "5 as 2, C++ select fenced, b",
                         "6 one mov under EXEC mask, f", "6 one mov under EXEC mask, b",
-                        "7 as 6, loads 3 ahead, fwd", "7 as 6, loads 3 ahead, bwd"};
+                        "7 as 6, loads 3 ahead, fwd", "7 as 6, loads 3 ahead, bwd",
+                        "8 no capture, store/step, f", "8 no capture, store/step, b"};
     for (int threads : {64, 512}) {
-        u64 hp[32] = {};  // the first of the two repeats
+        u64 hp[36] = {};  // the first of the two repeats
         for (int it = 0; it < 2; it++) {
             if (it == 1 && hipMemcpy(hp, dc, sizeof(hp), hipMemcpyDeviceToHost)) return 1;
             for (int m = 0; m < NM; m++) {
@@ -628,6 +642,8 @@ static int mfma4_modes(double *o) {
                 if (m == 17) hipLaunchKernelGGL((km<14, 6>), 1, threads, 0, 0, dF, dt, dout, o, dc);
                 if (m == 18) hipLaunchKernelGGL((km<13, 7>), 1, threads, 0, 0, dF, dt, dout, o, dc);
                 if (m == 19) hipLaunchKernelGGL((km<14, 7>), 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 20) hipLaunchKernelGGL((km<13, 8>), 1, threads, 0, 0, dF, dt, dout, o, dc);
+                if (m == 21) hipLaunchKernelGGL((km<14, 8>), 1, threads, 0, 0, dF, dt, dout, o, dc);
                 if (hipMemcpy(ho[m], dout, sizeof(gt), hipMemcpyDeviceToHost)) return 1;
             }
         }
