@@ -44,21 +44,14 @@ lib: $(LIB)
 oracle: $(ORACLE)
 harness: $(HARNESS) $(EMU) $(EMU64) $(SHIMT) $(REPLANX) $(DETECTH) $(MFMODEL) $(STMODEL)
 
-$(LIBDIR)/impc_qp.o: $(CSRC)/impc_qp.hip $(CSRC)/admm_core.hpp $(CSRC)/symbolic.hpp $(CSRC)/mpc_wave.hpp \
-		$(CSRC)/mpc_structure.hpp $(CSRC)/select.hpp $(CSRC)/mpc_build.hpp $(CSRC)/mpc_qp_internal.hpp \
-		$(CSRC)/fanout.hpp $(CSRC)/predict.hpp $(CSRC)/comm.hpp $(CSRC)/reftraj.hpp $(ROOT)/include/impc_qp.h $(ROOT)/include/impc_select.h \
-		$(ROOT)/include/impc_mpc.h $(ROOT)/include/impc_fanout.h $(ROOT)/include/impc_predict.h $(ROOT)/include/impc_comm.h \
-		$(SRCS)
+# (every source and header of the library: the build identity above is taken over the same list)
+$(LIBDIR)/impc_qp.o: $(CSRC)/impc_qp.hip $(SRCS)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) $(call IDFLAGS,) -c $< -o $@
 
 # section-profiling variant of the library (tools/section_profile.py; never the product)
 prof: $(PROFLIB)
-$(LIBDIR)/impc_qp_prof.o: $(CSRC)/impc_qp.hip $(CSRC)/admm_core.hpp $(CSRC)/symbolic.hpp $(CSRC)/mpc_wave.hpp \
-		$(CSRC)/mpc_structure.hpp $(CSRC)/select.hpp $(CSRC)/mpc_build.hpp $(CSRC)/mpc_qp_internal.hpp \
-		$(CSRC)/fanout.hpp $(CSRC)/predict.hpp $(CSRC)/comm.hpp $(CSRC)/reftraj.hpp $(ROOT)/include/impc_qp.h $(ROOT)/include/impc_select.h $(ROOT)/include/impc_mpc.h \
-		$(ROOT)/include/impc_fanout.h $(ROOT)/include/impc_predict.h $(ROOT)/include/impc_detect.h \
-		$(CSRC)/detect.hpp $(CSRC)/detect_gate.hpp
+$(LIBDIR)/impc_qp_prof.o: $(CSRC)/impc_qp.hip $(SRCS)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) $(call IDFLAGS,-prof) -DIMPC_SECTION_PROF -c $< -o $@
 $(PROFLIB): $(LIBDIR)/impc_qp_prof.o $(LIBDIR)/replan_run.o $(LIBDIR)/symbolic.o $(LIBDIR)/mpc_qp.o $(LIBDIR)/mpc_structure.o $(LIBDIR)/minsnap.o

@@ -229,14 +229,11 @@ __global__ __launch_bounds__(kBlock) void k_update_bounds(impc::DevSym sy, impc:
 // Team policy of mpc_wave.hpp on gfx950: one QP per workgroup of NL threads (NL/64 wavefronts);
 // LDS exchange + workgroup barrier, readlane broadcast inside a wavefront, butterfly reductions
 // inside a wavefront combined across wavefronts through LDS in a fixed order (bitwise uniform).
-// IMPC_LCOMB (the product since round 7; 0: A/B variants only): the team reductions' combine across
-// wavefronts in one lane per value instead of in every lane.  The termination check reduces 17
-// maxima and 2 sums; combined in every lane that was 76 LDS reads and 57 three-instruction maxima
-// per lane and check, all 256 lanes computing the same 19 numbers (config 3: 210.35 / 210.35 ->
-// 206.83 / 206.78 ms per launch, identical outputs; profiles/r07/README.md)
-#ifndef IMPC_LCOMB
-#define IMPC_LCOMB 1
-#endif
+// The team reductions' combine across wavefronts runs in one lane per value instead of in every lane
+// (round 7).  The termination check reduces 17 maxima and 2 sums; combined in every lane that was 76
+// LDS reads and 57 three-instruction maxima per lane and check, all 256 lanes computing the same 19
+// numbers (config 3: 210.35 / 210.35 -> 206.83 / 206.78 ms per launch, identical outputs;
+// profiles/r07/README.md)
 // LEAN (the three-teams-per-CU instance): a reduction's LDS slot is addressed from a thread index the
 // optimiser cannot see through, so the address is formed where it is used and no register (or spill
 // slot, reloaded inside the ADMM loop's time-limit test) carries it across the loop.
@@ -407,7 +404,6 @@ struct GpuTeam {
         }
         if ((threadIdx.x & 63) == 0) _Pragma("unroll") for (int k = 0; k < KS; k++) red[w * KT + KM + k] = sm[k];
         __syncthreads();
-#if IMPC_LCOMB
         // Combine across wavefronts in one lane per value instead of every lane combining all KT:
         // lane k of each wavefront takes value k's NL / 64 partials in wavefront order, as the
         // every-lane form below does (the same bits), and v_readlane hands each result to the whole
@@ -428,7 +424,7 @@ struct GpuTeam {
             __syncthreads();
             return;
         }
-#endif
+        // the one-wavefront team (NL = 64): every lane takes each value
         _Pragma("unroll") for (int k = 0; k < KM; k++) {
             double r = red[k];
             for (int u = 1; u < NL / 64; u++) r = vmax(r, red[u * KT + k]);

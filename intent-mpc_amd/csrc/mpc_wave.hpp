@@ -52,96 +52,23 @@ namespace impc {
 
 #define IMPC_WF __host__ __device__ __forceinline__
 
-// Phase-cost experiments (tools/exp.sh only): IMPC_DUP=<section id> runs that idempotent phase of
-// the ADMM iteration twice; the bench's time difference is the phase's marginal cost.
-// The serial recursions' wavefront at a raised issue priority (s_setprio) while it runs them: the
+// The serial recursions' wavefront at a raised issue priority (s_setprio 2) while it runs them: the
 // co-resident team's waves share its SIMD, and the recursion is the team's critical path (round 6:
 // config 3 213.9 / 214.1 -> 210.8 / 210.5 ms per launch at priority 2, 211.1 / 211.2 at 3; identical
-// iterations; 0 = off)
-#ifndef IMPC_PRIO
-#define IMPC_PRIO 2
-#endif
-#if IMPC_PRIO && defined(__HIP_DEVICE_COMPILE__)
-#define IMPC_PRIO_UP() __builtin_amdgcn_s_setprio(IMPC_PRIO)
+// iterations)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define IMPC_PRIO_UP() __builtin_amdgcn_s_setprio(2)
 #define IMPC_PRIO_DOWN() __builtin_amdgcn_s_setprio(0)
 #else
 #define IMPC_PRIO_UP() ((void)0)
 #define IMPC_PRIO_DOWN() ((void)0)
 #endif
-// The fully unrolled default-horizon stage recursions on the four-block FP64 matrix instruction
-// (sweep_mfma below) instead of the 8x8 lane grid; device code only, 0 = the lane grid (A/B variants).
-#ifndef IMPC_SWEEP_MFMA
-#define IMPC_SWEEP_MFMA 1
-#endif
-#if IMPC_SWEEP_MFMA && defined(__HIP_DEVICE_COMPILE__)
-#define IMPC_SWEEP_MFMA_DEV 1
-#else
-#define IMPC_SWEEP_MFMA_DEV 0
-#endif
-// What the default horizon's matrix-instruction sweeps do around their steps (round 12; 0: the
-// round-11 form, A/B variants only; profiles/r12/kernel_ab.txt):
-// IMPC_SWEEP_PRO: the sweeping wavefront forms its lane maps and store addresses and issues its
-// first F reads in front of the barrier that releases the sweep (config 3: 145.7-146.3 -> 143.9-144.0
-// ms per launch)
-// IMPC_SWEEP_EARLY: a capture register is scaled back and stored behind its last step (with the
-// prologue: -> 142.2-142.4 ms; without it the store addresses are formed between the steps and it
-// measured slower than the parent, 147.3-147.4)
-#ifndef IMPC_SWEEP_PRO
-#define IMPC_SWEEP_PRO 1
-#endif
-#ifndef IMPC_SWEEP_EARLY
-#define IMPC_SWEEP_EARLY 1
-#endif
+// Phase-cost experiments (tools/exp.sh only): IMPC_DUP=<section id> runs that idempotent phase of
+// the ADMM iteration twice; the bench's time difference is the phase's marginal cost.
 #ifndef IMPC_DUP
 #define IMPC_DUP -1
 #endif
-#ifndef IMPC_CHDUP
-#define IMPC_CHDUP 0
-#endif
-// A/B switch (tools/exp.sh variants only): IMPC_CHUNK19=1 runs the default horizon's (W = 19)
-// stage recursions in chunks too (the long shape's form, chunks of 6 / 6 / 6 / 1 steps), their
-// operators in an LDS region past the products (the one-slot shape's F region has no tail)
-#ifndef IMPC_CHUNK19
-#define IMPC_CHUNK19 0
-#endif
-// The long shape's sweeps in five chunks on the four wavefronts (CL = 2 ceil(W/10): W = 39 -> 8, 8,
-// 8, 8, 7; the product since round 5).  IMPC_CHUNK5=0 (A/B variants only): the round-4 four-chunk
-// form (W = 39 -> 10, 10, 10, 9), measured 1251.6 vs 1209.6 ms per config-5 launch
-#ifndef IMPC_CHUNK5
-#define IMPC_CHUNK5 1
-#endif
-// The factorisation's latency form (round 5; IMPC_FACT2=0: the round-4 loops, A/B variants only):
-// assembly codes loaded four at a time with the next stage's ranges prefetched, the Gauss-Jordan
-// steps' operands read at once, the 13-term products unrolled.  The long shape's setup runs one
-// team per CU, so these latencies are exposed: setup 0.440 -> 0.358 ms per N = 40 QP, config 5's
-// closed loop 626 -> 608 ms per step (profiles/r05/exp_phase/README.md)
-#ifndef IMPC_FACT2
-#define IMPC_FACT2 1
-#endif
-// A/B knobs of that form (variants only): the 13-term products' unroll count (0 = full) and the
-// assembly's codes per batch
-#ifndef IMPC_F2U
-#define IMPC_F2U 0
-#endif
-// The long shape's factorisation (IMPC_FACT3, on for VS = 3 only): the Schur complement E_k kept
-// in the register of the lane that assembles M_k+1's matching entry (the destinations are assigned
-// so that lane 8i + j computes E[i][j] and assembles M[i][j]), B_k double-buffered by stage parity,
-// and the barrier between E_k and the next stage's assembly dropped.  Config 5's closed loop
-// 610.9 -> 604.0 ms; on the default horizon it measured 214.3 -> 215.2 ms, so that shape keeps the
-// barrier (profiles/r05/exp_phase/README.md)
-#ifndef IMPC_FACT3
-#define IMPC_FACT3 1
-#endif
-#define IMPC_PRAGMA_(x) _Pragma(#x)
-#define IMPC_PRAGMA(x) IMPC_PRAGMA_(x)
-#ifndef IMPC_F2B
-#define IMPC_F2B 4
-#endif
 #define IMPC_REP(X) for (int rep_ = 0; rep_ < (IMPC_DUP == (X) ? 2 : 1); rep_++)
-// Branch counters of the CPU emulation's instrumented builds (tools only; nothing in the product)
-#ifndef IMPC_COUNT
-#define IMPC_COUNT(X) ((void)0)
-#endif
 
 // Variants measured slower and removed in round 4 (their numbers stay in profiles/r0*/exp/README.md,
 // their code in git history): the twisted two-ended elimination, pair-blocked and chunked stage
@@ -149,6 +76,20 @@ namespace impc {
 // captures, split dot-product chains, opaque phase bases, delta-less update instances, per-step
 // history / store captures, (c, S)-carried sweeps, off-chip scaling vectors, Cholesky / 1x1-pivot
 // stage inverses.  What is left is the measured-best form of each phase.
+// Removed in round 13, each a build switch beside its successor until then (commit 60fcdf2 is the
+// last that holds their code; the numbers are in profiles/r0*/ and profiles/r1*/): the round-4
+// factorisation loops (IMPC_FACT2=0; setup 0.440 vs 0.358 ms per N = 40 QP) and the long shape's
+// factorisation with the barrier between E_k and the next assembly (IMPC_FACT3=0; config 5 610.9 vs
+// 604.0 ms), partial unrolls of the 13-term products and other assembly batch sizes (IMPC_F2U,
+// IMPC_F2B), the four-chunk long-horizon sweeps (IMPC_CHUNK5=0; 1251.6 vs 1209.6 ms per config-5
+// launch), the default horizon in chunks with an LDS region of its own (IMPC_CHUNK19; slower at two
+// teams per CU) and the chunk rounds' repeat loops (IMPC_CHDUP), the lane-grid default-horizon sweep
+// in device code (IMPC_SWEEP_MFMA=0; config 3 184.0 vs 171.8-171.9 ms), the matrix-instruction sweep
+// without its prologue in front of the barrier or its early stores (IMPC_SWEEP_PRO / IMPC_SWEEP_EARLY
+// = 0; 145.7-146.3 and 143.9-144.0 vs 142.2-142.4 ms; early stores without the prologue 147.3-147.4),
+// recursion priorities other than 2 (IMPC_PRIO), the every-lane team-reduction combine of the
+// four-wavefront team (IMPC_LCOMB=0 in impc_qp.hip; 210.35 vs 206.8 ms) and the emulation's branch
+// counters (IMPC_COUNT, defined by nothing).
 
 // Scheduling hint for the parallel phases' LDS reads: under the kernel's register pressure the
 // machine scheduler otherwise issues them one ds_read2 at a time, each followed by its own
@@ -304,11 +245,8 @@ struct WaveLds {
         return c > f ? c : f;
     }
     static IMPC_WF int p_size(const WaveTables &T) { return p_size(T.CG, T.n, T.HS, T.mg, T.T1r); }
-    // the chunk operators' region of the one-slot shape (IMPC_CHUNK19), after the products
-    static constexpr int CHX = (VS == 1 && IMPC_CHUNK19) ? 448 : 0;
-    static IMPC_WF int ch_off(const WaveTables &T) { return P_OFF + p_size(T) + 8; }
     // D, E in LDS for a shape without them in the fixed layout (WaveTables::scal_lds)
-    static IMPC_WF int scl2_off(const WaveTables &T) { return P_OFF + p_size(T) + 8 + CHX; }
+    static IMPC_WF int scl2_off(const WaveTables &T) { return P_OFF + p_size(T) + 8; }
     static IMPC_WF int size(const WaveTables &T) {
         return scl2_off(T) + (!ONCHIP && T.scal_lds ? 2 * T.n + T.mg : 0);
     }
@@ -317,7 +255,7 @@ struct WaveLds {
                          DIAGX = FE + 64;
     // general rows' rho during the factorisation: products region + 4 mg
     static_assert(DIAGX + NMAX <= RED_OFF, "factorisation scratch does not fit");
-    // the coupling block of odd stages (IMPC_FACT3: B_k double-buffered by stage parity)
+    // the coupling block of odd stages (the long shape's B_k is double-buffered by stage parity)
     static constexpr int FB2 = DIAGX + NMAX;
     static_assert(VS != 3 || FB2 + 104 <= RED_OFF, "factorisation scratch does not fit");
 };
@@ -530,40 +468,38 @@ struct WaveQP {
     IMPC_WF double *xbuf() { return lds + LD::X_OFF; }
     IMPC_WF double *pbuf() { return lds + LD::P_OFF; }
 
+    // The long shape's factorisation keeps the Schur complement E_k in the register of the lane that
+    // assembles M_k+1's matching entry (the destinations are assigned so that lane 8i + j computes
+    // E[i][j] and assembles M[i][j]), double-buffers B_k by stage parity and drops the barrier between
+    // E_k and the next stage's assembly.  Config 5's closed loop 610.9 -> 604.0 ms; on the default
+    // horizon it measured 214.3 -> 215.2 ms, so that shape keeps the barrier
+    // (profiles/r05/exp_phase/README.md)
+    static constexpr bool F3 = VS == 3;
+
     // Chunked stage recursions of the long horizon (the compile-time W = 39 and W = 29 instances of
     // the three-slot shape).  That shape runs one team per CU, so the three wavefronts that wait out
-    // a serial sweep leave their SIMDs idle.  Each W-step sweep runs as four chunks, CL = 2 ceil(W/8)
-    // steps each and W - 3 CL in the last (W = 39: 10, 10, 10, 9; W = 29: 8, 8, 8, 5), one per
-    // wavefront, in two rounds: wave 0 runs the first chunk from the true start while waves 1 and 2
-    // run theirs from zero for the chunk-end values only; after a barrier each of waves 1..3 forms
-    // its chunk's true start from those ends and the chunk operators (products of the chunk's -F_k,
-    // or -F_k^T backward, built with the factorisation: a_{o+CL} = a^_{o+CL} + P a_o) in one 8-lane
-    // reduction and runs its chunk again.  Dependent chain per sweep: W steps -> 2 CL steps and one
-    // reduction.  Operators and ends live in the F region's tail (blocks >= W + 3, never read).
-    // CL is even, so every chunk starts on an even stage (the sweeps' index parity).
-    //
-    // Five chunks (NCH = 5, the long shape's form since round 5; four: IMPC_CHUNK5=0 and the
-    // default horizon's IMPC_CHUNK19 variant): CL = 2 ceil(W/10) and W - 4 CL in the
-    // last (W = 39: 8, 8, 8, 8, 7; W = 29: 6, 6, 6, 6, 5).  Round 1: wave 0 the first chunk from the
-    // true start, waves 1..3 chunks 1..3 from zero; round 2: waves 1..3 chunks 1..3 again from their
-    // true starts and wave 0 the fifth, whose start a_4CL = a^_4CL + P3 a^_3CL + P3P2 a^_2CL +
-    // P3P2P1 a_CL is still one 8-lane reduction.  Chain per sweep: 2 CL steps and one reduction
-    // (W = 39: 16 instead of 20).
-    static constexpr bool F3 = IMPC_FACT2 && IMPC_FACT3 && VS == 3;
-    static constexpr int NCH = (WF > 0 && VS == 3 && IMPC_CHUNK5) ? 5 : 4;
-    static constexpr bool CHUNK = WF > 0 && NL == 256 && (VS == 3 || (VS == 1 && IMPC_CHUNK19 != 0));
-    static constexpr int CL = WF > 0 ? (NCH == 5 ? 2 * ((WF + 9) / 10) : 2 * ((WF + 7) / 8)) : 2;
-    static constexpr int CLAST = WF - (NCH - 1) * CL;
+    // a serial sweep leave their SIMDs idle.  Each W-step sweep runs as five chunks on the four
+    // wavefronts, CL = 2 ceil(W/10) steps each and W - 4 CL in the last (W = 39: 8, 8, 8, 8, 7;
+    // W = 29: 6, 6, 6, 6, 5), in two rounds.  Round 1: wave 0 runs the first chunk from the true start
+    // while waves 1..3 run chunks 1..3 from zero for the chunk-end values only.  After a barrier,
+    // round 2: each of waves 1..3 forms its chunk's true start from those ends and the chunk operators
+    // (products of the chunk's -F_k, or -F_k^T backward, built with the factorisation:
+    // a_{o+CL} = a^_{o+CL} + P a_o) in one 8-lane reduction and runs its chunk again, and wave 0 runs
+    // the fifth, whose start a_4CL = a^_4CL + P3 a^_3CL + P3P2 a^_2CL + P3P2P1 a_CL is still one
+    // 8-lane reduction.  Dependent chain per sweep: W steps -> 2 CL steps and one reduction (W = 39:
+    // 16; the round-4 form, four chunks of 2 ceil(W/8), had 20 and measured 1251.6 vs 1209.6 ms per
+    // config-5 launch).  Operators and ends live in the F region's tail (blocks >= W + 3, never
+    // read).  CL is even, so every chunk starts on an even stage (the sweeps' index parity).
+    static constexpr bool CHUNK = WF > 0 && NL == 256 && VS == 3;
+    static constexpr int CL = WF > 0 ? 2 * ((WF + 9) / 10) : 2;
+    static constexpr int CLAST = WF - 4 * CL;
     static constexpr int CH_OFF = LD::F_OFF + 64 * (WF + 3);
-    enum { kChFP1 = 0, kChFP2 = 64, kChFP21 = 128, kChBT1 = 192, kChBT2 = 256, kChBT21 = 320 };
-    // five chunks: forward P1 P2 P3 P2P1 P3P2 P3P2P1, then the same backward (+kCh5B), then the ends
-    enum { kCh5P1 = 0, kCh5P2 = 64, kCh5P3 = 128, kCh5P21 = 192, kCh5P32 = 256, kCh5P321 = 320, kCh5B = 384 };
-    static constexpr int kChEnd = NCH == 5 ? 768 : 384;
-    static constexpr int kChEnds = NCH == 5 ? 24 : 16;  // chunk-end values per direction
-    static_assert(!CHUNK || VS == 1 || CH_OFF + kChEnd + 2 * kChEnds <= LD::R_OFF,
-                  "chunk operators do not fit the F region");
-    static_assert(!CHUNK || VS != 1 || LD::CHX >= kChEnd + 2 * kChEnds, "chunk operator region");
-    IMPC_WF double *chbuf() const { return lds + (VS == 1 ? LD::ch_off(T) : CH_OFF); }
+    // forward P1 P2 P3 P2P1 P3P2 P3P2P1, then the same backward (+kChB), then the ends
+    enum { kChP1 = 0, kChP2 = 64, kChP3 = 128, kChP21 = 192, kChP32 = 256, kChP321 = 320, kChB = 384 };
+    static constexpr int kChEnd = 768;
+    static constexpr int kChEnds = 24;  // chunk-end values per direction
+    static_assert(!CHUNK || CH_OFF + kChEnd + 2 * kChEnds <= LD::R_OFF, "chunk operators do not fit the F region");
+    IMPC_WF double *chbuf() const { return lds + CH_OFF; }
     static_assert(!CHUNK || (CLAST >= 1 && CLAST <= CL), "chunk lengths");
 
     // zero the exchange vectors (their tails are the zero slots read by padded entries)
@@ -753,7 +689,6 @@ struct WaveQP {
         _Pragma("unroll") for (int s = 0; s < GS; s++) Eg[s] = 1.0;
         c = 1.0;
         double *pb = pbuf(), *xb = xbuf();
-#if IMPC_FACT2
         // |A| entries of the general rows -> products buffer: pass 0's here, each later pass's at
         // the end of the pass before (after its scaling), ordered by that pass's team reduction
         if (st.scaling > 0) {
@@ -763,16 +698,7 @@ struct WaveQP {
             }
             wv.sync();
         }
-#endif
         for (int it = 0; it < st.scaling; it++) {
-#if !IMPC_FACT2
-            // |A| entries of general rows -> products buffer
-            _Pragma("unroll") for (int s = 0; s < GS; s++) {
-                if (gok[s])
-                    _Pragma("unroll") for (int e = 0; e < 4; e++) pb[gdst(s, e)] = fabs(a[s][e]);
-            }
-            wv.sync();
-#endif
             double Dt[VS], Etb[VS], Etg[GS];
             _Pragma("unroll") for (int s = 0; s < VS; s++) {
                 // colnorm_sym(P) (diagonal), max with colnorm(A) = max(box, general entries)
@@ -810,14 +736,12 @@ struct WaveQP {
                 _Pragma("unroll") for (int e = 0; e < 4; e++) a[s][e] = (a[s][e] * Etg[s]) * xb[gcol(s, e)];
                 Eg[s] = Eg[s] * Etg[s];
             }
-#if IMPC_FACT2
             // the next pass's |A| (every read of this pass's came before the D_temp barrier)
             if (it + 1 < st.scaling)
                 _Pragma("unroll") for (int s = 0; s < GS; s++) {
                     if (gok[s])
                         _Pragma("unroll") for (int e = 0; e < 4; e++) pb[gdst(s, e)] = fabs(a[s][e]);
                 }
-#endif
             // cost normalisation
             double psum = 0.0, qn = 0.0;
             _Pragma("unroll") for (int s = 0; s < VS; s++) {
@@ -826,16 +750,12 @@ struct WaveQP {
                     qn = dmax(fabs(q[s]), qn);
                 }
             }
-#if IMPC_FACT2
-            // both cost norms in one team reduction (the same combine orders as sum / max)
+            // both cost norms in one team reduction (the same combine orders as sum / max; its
+            // barriers also order this pass's reads of pb / xb before the next pass's writes)
             double mx1[1] = {qn}, sm1[1] = {psum};
             wv.max_sum_n(mx1, sm1);
             double ct = sm1[0] / (double)n;
             qn = mx1[0];
-#else
-            double ct = wv.sum(psum) / (double)n;
-            qn = wv.max(qn);
-#endif
             qn = qn < kMinScaling ? 1.0 : qn;
             qn = qn > kMaxScaling ? kMaxScaling : qn;
             ct = dmax(ct, qn);
@@ -853,10 +773,6 @@ struct WaveQP {
                 q[s] *= ct;
             }
             c *= ct;
-#if !IMPC_FACT2
-            wv.sync();  // (redundant: the team reduction's barriers already order this pass's reads
-                        // of pb / xb before the next pass's writes)
-#endif
         }
         c = wv.uniform(c);
         cinv = 1. / c;
@@ -883,7 +799,7 @@ struct WaveQP {
     // ------------------------------------------------------------ block factorisation
     // Returns 1 if a pivot is not positive (OSQP_NONCVX_ERROR).
     // the factorisation assembly's destination of slot r = L + NL u (0 <= r < kStageDests): the
-    // identity, or (IMPC_FACT3) slots 0..63 on the 8 x 8 Schur block M[i][j] (13 i + j, lane 8 i + j),
+    // identity, or (F3) slots 0..63 on the 8 x 8 Schur block M[i][j] (13 i + j, lane 8 i + j),
     // the rest in order over the other 209 (M rows 0..7 columns 8..12, M rows 8..12, then B)
     IMPC_WF static int stage_dest(int r) {
         if constexpr (F3) {
@@ -894,6 +810,11 @@ struct WaveQP {
         return r;
     }
 
+    // Written for latency (round 5): the assembly codes loaded four at a time with the next stage's
+    // ranges prefetched, the Gauss-Jordan steps' operands read at once, the 13-term products fully
+    // unrolled.  The long shape's setup runs one team per CU, so these latencies are exposed: setup
+    // 0.440 -> 0.358 ms per N = 40 QP against the round-4 loops, config 5's closed loop 626 -> 608 ms
+    // per step (profiles/r05/exp_phase/README.md)
     IMPC_WF int factorize() {
         const int n = T.n, W = Wst(), N = W + 1;
         double *w = pbuf(), *rhog = pbuf() + 4 * T.mg, *diagx = lds + LD::DIAGX;
@@ -915,7 +836,6 @@ struct WaveQP {
         }
         wv.sync();
         int bad = 0;
-#if IMPC_FACT2
         // the assembly program's range of each of this lane's destinations, one stage ahead (a
         // global load; the long shape runs one team per CU, so nothing hides its latency)
         constexpr int ND = (kStageDests + NL - 1) / NL;
@@ -929,53 +849,39 @@ struct WaveQP {
             }
         };
         load_tp(0);
-#endif
+        constexpr int kCodes = 4;  // assembly codes per batch
         for (int k = 0; k < N; k++) {
             const int sz = k < W ? 13 : 8;
             if constexpr (F3) Bb = lds + ((k & 1) ? LD::FB2 : LD::FB);
             // assemble M_kk and Bbar_k
-#if IMPC_FACT2
             int32_t tc[ND][2];
             _Pragma("unroll") for (int u = 0; u < ND; u++) tc[u][0] = tp[u][0], tc[u][1] = tp[u][1];
             load_tp(k + 1);
             _Pragma("unroll") for (int u = 0; u < ND; u++) {
                 if (L + NL * u >= kStageDests) continue;
                 const int d = stage_dest(L + NL * u);
-#else
-            for (int d = L; d < kStageDests; d += NL) {
-#endif
                 const bool isB = d >= 169;
                 if (isB && k == W) continue;
                 const int dd = isB ? d - 169 : d;
                 const int r = dd / 13, cc = dd % 13;
                 double val = 0.0;
                 if (isB || (r < sz && cc < sz)) {
-#if IMPC_FACT2
                     // the codes four at a time, their LDS operands before the products (the sum
                     // keeps its term order)
                     const int32_t t0 = tc[u][0], t1 = tc[u][1];
-                    for (int32_t t = t0; t < t1; t += IMPC_F2B) {
-                        int32_t cd[IMPC_F2B];
-                        _Pragma("unroll") for (int v = 0; v < IMPC_F2B; v++) cd[v] = t + v < t1 ? T.term[t + v] : 0;
-                        double rg[IMPC_F2B], we[IMPC_F2B], wf[IMPC_F2B];
-                        _Pragma("unroll") for (int v = 0; v < IMPC_F2B; v++) {
+                    for (int32_t t = t0; t < t1; t += kCodes) {
+                        int32_t cd[kCodes];
+                        _Pragma("unroll") for (int v = 0; v < kCodes; v++) cd[v] = t + v < t1 ? T.term[t + v] : 0;
+                        double rg[kCodes], we[kCodes], wf[kCodes];
+                        _Pragma("unroll") for (int v = 0; v < kCodes; v++) {
                             const int32_t g = cd[v] >> 4, e = (cd[v] >> 2) & 3, f = cd[v] & 3;
                             rg[v] = rhog[g];
                             we[v] = w[4 * g + e];
                             wf[v] = w[4 * g + f];
                         }
-                        _Pragma("unroll") for (int v = 0; v < IMPC_F2B; v++)
+                        _Pragma("unroll") for (int v = 0; v < kCodes; v++)
                             if (t + v < t1) val += rg[v] * we[v] * wf[v];
                     }
-#else
-                    const int32_t t0 = T.term_ptr[(int64_t)k * kStageDests + d];
-                    const int32_t t1 = T.term_ptr[(int64_t)k * kStageDests + d + 1];
-                    for (int32_t t = t0; t < t1; t++) {
-                        int32_t code = T.term[t];
-                        int32_t g = code >> 4, e = (code >> 2) & 3, f = code & 3;
-                        val += rhog[g] * w[4 * g + e] * w[4 * g + f];
-                    }
-#endif
                     if (!isB && r == cc) val += diagx[13 * k + r];
                     if (!isB && k > 0 && r < 8 && cc < 8)  // Schur complement (F3: this lane's E)
                         val -= F3 ? e_reg : E[8 * r + cc];
@@ -1006,9 +912,8 @@ struct WaveQP {
                         if (gi >= sz || gc >= sz) continue;
                         const int i = last && gc > gi ? gc : gi, c = last && gc > gi ? gi : gc;
                         double v;
-#if IMPC_FACT2
                         // every operand read at once (one LDS round trip per step), the lane's
-                        // case selected after: the same expressions as below
+                        // case selected after
                         const double p00 = src[13 * j + j], p01 = src[13 * j + (two ? j + 1 : j)];
                         const double p10 = src[13 * (two ? j + 1 : j) + j], p11 = src[13 * (two ? j + 1 : j) + (two ? j + 1 : j)];
                         const double s0 = src[13 * j + c], s1 = src[13 * (two ? j + 1 : j) + c];
@@ -1032,43 +937,6 @@ struct WaveQP {
                             const double r = 1.0 / p00;
                             v = i == j ? (c == j ? r : s0 * r) : (c == j ? -(a0 * r) : sic - (a0 * r) * s0);
                         }
-#else
-                        if (two) {
-                            const double p00 = src[13 * j + j], p01 = src[13 * j + j + 1];
-                            const double p10 = src[13 * (j + 1) + j], p11 = src[13 * (j + 1) + j + 1];
-                            const double det = p00 * p11 - p01 * p10;
-                            if (!(p00 > 0.0) || !(det > 0.0)) bad = 1;
-                            const double rd = 1.0 / det;
-                            const double q00 = p11 * rd, q01 = -(p01 * rd), q10 = -(p10 * rd), q11 = p00 * rd;
-                            const int ri = i - j, ci = c - j;
-                            const bool iJ = ri == 0 || ri == 1, cJ = ci == 0 || ci == 1;
-                            if (iJ && cJ) {
-                                v = ri == 0 ? (ci == 0 ? q00 : q01) : (ci == 0 ? q10 : q11);
-                            } else if (iJ) {
-                                const double s0 = src[13 * j + c], s1 = src[13 * (j + 1) + c];
-                                v = ri == 0 ? q00 * s0 + q01 * s1 : q10 * s0 + q11 * s1;
-                            } else {
-                                const double a0 = src[13 * i + j], a1 = src[13 * i + j + 1];
-                                const double u0 = a0 * q00 + a1 * q10, u1 = a0 * q01 + a1 * q11;
-                                if (cJ)
-                                    v = -(ci == 0 ? u0 : u1);
-                                else
-                                    v = src[13 * i + c] - (u0 * src[13 * j + c] + u1 * src[13 * (j + 1) + c]);
-                            }
-                        } else {
-                            const double p = src[13 * j + j];
-                            if (!(p > 0.0)) bad = 1;
-                            const double r = 1.0 / p;
-                            if (i == j && c == j)
-                                v = r;
-                            else if (i == j)
-                                v = src[13 * j + c] * r;
-                            else if (c == j)
-                                v = -(src[13 * i + j] * r);
-                            else
-                                v = src[13 * i + c] - (src[13 * i + j] * r) * src[13 * j + c];
-                        }
-#endif
                         (last ? Ai : dst)[13 * gi + gc] = v;
                     }
                     wv.sync();
@@ -1084,24 +952,14 @@ struct WaveQP {
                 for (int p = L; p < 104; p += NL) {
                     int i = p / 13, cc = p % 13;
                     double s = 0.0;
-#if IMPC_FACT2 && IMPC_F2U == 0
-                    _Pragma("unroll")
-#elif IMPC_FACT2
-                    IMPC_PRAGMA(unroll IMPC_F2U)
-#endif
-                    for (int t = 0; t < 13; t++) s += Bb[13 * i + t] * Ai[13 * t + cc];
+                    _Pragma("unroll") for (int t = 0; t < 13; t++) s += Bb[13 * i + t] * Ai[13 * t + cc];
                     G[p] = s;
                 }
                 wv.sync();
                 if (L < 64) {
                     int i = L >> 3, j = L & 7;
                     double s = 0.0;
-#if IMPC_FACT2 && IMPC_F2U == 0
-                    _Pragma("unroll")
-#elif IMPC_FACT2
-                    IMPC_PRAGMA(unroll IMPC_F2U)
-#endif
-                    for (int t = 0; t < 13; t++) s += G[13 * i + t] * Bb[13 * j + t];
+                    _Pragma("unroll") for (int t = 0; t < 13; t++) s += G[13 * i + t] * Bb[13 * j + t];
                     if constexpr (F3)
                         e_reg = s;
                     else
@@ -1138,43 +996,6 @@ struct WaveQP {
         return -(!(k & 1) ? Fm[64 * k + 8 * c + r] : Fm[64 * k + 8 * r + c]);  // mfmap::f_slot
     }
 
-    // The chunk operators (CHUNK): wave 0 / 1 the forward chunks 1 / 2 (steps CL..2CL-1 /
-    // 2CL..3CL-1, P <- -F_k P with k ascending), wave 2 / 3 the backward chunks 1 / 2 (steps
-    // 3CL-1..2CL / 2CL-1..CL, P <- -F_k^T P with k descending); lane (i, j) holds P[i][j].  Then the
-    // two-chunk operators of the last chunk's start, P2 P1, forward and backward.
-    IMPC_WF void chunk_ops() {
-        if constexpr (NCH == 5) {
-            chunk_ops5();
-            return;
-        }
-        const double *Fm = F();
-        double *C = chbuf();
-        const int w = L >> 6, l = L & 63, i = l >> 3, j = l & 7;
-        const bool fwd = w < 2;
-        const int o = (w == 0 || w == 3) ? CL : 2 * CL;
-        double *P = C + (fwd ? kChFP1 + 64 * w : kChBT1 + 64 * (w - 2));
-        P[l] = i == j ? 1.0 : 0.0;
-        wv.wsync();
-        for (int s = 0; s < CL; s++) {
-            const int k = fwd ? o + s : o + CL - 1 - s;
-            double pc[8];
-            _Pragma("unroll") for (int m = 0; m < 8; m++) pc[m] = P[8 * m + j];
-            double v = 0.0;
-            _Pragma("unroll") for (int m = 0; m < 8; m++) v -= (fwd ? f_el(Fm, k, i, m) : f_el(Fm, k, m, i)) * pc[m];
-            wv.wsync();
-            P[l] = v;
-            wv.wsync();
-        }
-        wv.sync();
-        if (w == 0 || w == 2) {
-            const double *P1 = C + (w == 0 ? kChFP1 : kChBT1), *P2 = C + (w == 0 ? kChFP2 : kChBT2);
-            double v = 0.0;
-            _Pragma("unroll") for (int m = 0; m < 8; m++) v += P2[8 * i + m] * P1[8 * m + j];
-            C[(w == 0 ? kChFP21 : kChBT21) + l] = v;
-        }
-        wv.sync();
-    }
-
     // P = the product of one chunk's step operators on one wavefront (lane (i, j) holds P[i][j]):
     // forward steps o..o+CL-1, P <- -F_k P with k ascending; backward steps o+CL-1..o, P <- -F_k^T P
     // with k descending
@@ -1200,25 +1021,25 @@ struct WaveQP {
         _Pragma("unroll") for (int m = 0; m < 8; m++) v += A[8 * i + m] * B[8 * m + j];
         out[l] = v;
     }
-    // The five-chunk operators: forward chunks c = 1..3 start at c CL; backward chunks c = 1..3 (in
+    // The chunk operators (CHUNK): forward chunks c = 1..3 start at c CL; backward chunks c = 1..3 (in
     // sweep order) cover steps (5 - c) CL - 1 .. (4 - c) CL.  Six chunk products on four wavefronts,
     // then the two-chunk products, then the three-chunk ones.
-    IMPC_WF void chunk_ops5() {
-        double *C = chbuf(), *Bk = C + kCh5B;
+    IMPC_WF void chunk_ops() {
+        double *C = chbuf(), *Bk = C + kChB;
         const int w = L >> 6, l = L & 63;
         if (w < 3)
-            chunk_prod(true, (w + 1) * CL, C + kCh5P1 + 64 * w, l);
+            chunk_prod(true, (w + 1) * CL, C + kChP1 + 64 * w, l);
         else
-            chunk_prod(false, 3 * CL, Bk + kCh5P1, l);
-        if (w < 2) chunk_prod(false, (2 - w) * CL, Bk + kCh5P2 + 64 * w, l);
+            chunk_prod(false, 3 * CL, Bk + kChP1, l);
+        if (w < 2) chunk_prod(false, (2 - w) * CL, Bk + kChP2 + 64 * w, l);
         wv.sync();
         // w 0 / 1: forward P2 P1 / P3 P2; w 2 / 3: backward P2 P1 / P3 P2
         double *X = w < 2 ? C : Bk;
-        mat8(X + kCh5P2 + 64 * (w & 1), X + kCh5P1 + 64 * (w & 1), X + kCh5P21 + 64 * (w & 1), l);
+        mat8(X + kChP2 + 64 * (w & 1), X + kChP1 + 64 * (w & 1), X + kChP21 + 64 * (w & 1), l);
         wv.sync();
         if (w < 2) {  // w 0: forward P3 P2 P1, w 1: backward
             double *Y = w ? Bk : C;
-            mat8(Y + kCh5P3, Y + kCh5P21, Y + kCh5P321, l);
+            mat8(Y + kChP3, Y + kChP21, Y + kChP321, l);
         }
         wv.sync();
     }
@@ -1276,13 +1097,16 @@ struct WaveQP {
         }
     }
 
-    // The round-12 forms are for the default horizon's sweep (W = 19) in device code: the long
-    // shape's runtime-W instance keeps its W = 39 sweep as it was.
-    static constexpr bool kSweep19 = IMPC_SWEEP_MFMA_DEV && !CHUNK && LD::WSPEC == 19;
-    static constexpr bool kSweepPro = kSweep19 && IMPC_SWEEP_PRO != 0;
-    static constexpr bool kSweepEarly = kSweepPro && IMPC_SWEEP_EARLY != 0;
+    // The default horizon's sweep (W = 19) in device code runs in two parts, sweep_pro / sweep_run
+    // below (round 12; profiles/r12/kernel_ab.txt): the prologue in front of the releasing barrier
+    // took config 3 from 145.7-146.3 to 143.9-144.0 ms per launch, the early stores with it to
+    // 142.2-142.4 (early stores without the prologue form the store addresses between the steps and
+    // measured slower than the form without either, 147.3-147.4).  The long shape's runtime-W instance keeps its
+    // W = 39 sweep whole (sweep_mfma).
+#if defined(__HIP_DEVICE_COMPILE__)
+    static constexpr bool kSweep19 = !CHUNK && LD::WSPEC == 19;
 
-#if IMPC_SWEEP_MFMA_DEV
+    // The matrix-instruction sweeps (device code only; the CPU emulation keeps the 8x8 lane grid).
     // The select of capm by a lane mask given as a constant (mfmap::keep_mask)
     IMPC_WF static void capk(double &d, double r, uint64_t msk) {
         int lo = __double2loint(d), hi = __double2hiint(d);
@@ -1349,7 +1173,7 @@ struct WaveQP {
             *(m1 < WC ? ob + 13 * (FWD ? m1 + 1 : WC - 1 - m1) + os[1] : junk) = back * c1[q];
         }
     }
-    // The default horizon's sweep in two parts (kSweepPro; the same reads, steps, values and stores as
+    // The default horizon's sweep in two parts (kSweep19; the same reads, steps, values and stores as
     // sweep_mfma).  sweep_pro is what depends on neither cb's nor ob's content: the lane's F slots and
     // c indices by step parity, its element of the start vector, where it stores capture register q of
     // the even (s0) / odd (s1) steps -- the element it owns or its discard slot -- and the first
@@ -1386,7 +1210,7 @@ struct WaveQP {
             p.fq[q] = Fm[64 * (FWD ? q : WC - 1 - q) + p.fs[q & 1]];
         sweep_stores<WC, FWD>(p, ob);
     }
-    // The steps behind the barrier.  kSweepEarly: each capture register is scaled back and stored
+    // The steps behind the barrier.  Each capture register is scaled back and stored
     // behind the last step that writes it (mfmap::cap_final: c0[0] / c1[0] go out during steps 15-18),
     // so only the last steps' registers are left when the sweep ends.
     template <int WC, bool FWD>
@@ -1411,17 +1235,15 @@ struct WaveQP {
             double &c = (m & 1) ? c1[m >> 4] : c0[m >> 4];
             if ((m & 14) == 0) c = v;  // the register's first step
             else capk(c, v, mfmap::keep_mask((m >> 1) & 7, m & 1));
-            if constexpr (kSweepEarly) {
-                if (m == mfmap::cap_final(WC, m >> 4, m & 1)) *((m & 1) ? p.s1[m >> 4] : p.s0[m >> 4]) = back * c;
-            }
+            if (m == mfmap::cap_final(WC, m >> 4, m & 1)) *((m & 1) ? p.s1[m >> 4] : p.s0[m >> 4]) = back * c;
         }
         _Pragma("unroll") for (int q = 0; q < CQ; q++) {  // registers no step of this WC reaches
             if (16 * q >= WC) c0[q] = 0.0;
             if (16 * q + 1 >= WC) c1[q] = 0.0;
         }
         _Pragma("unroll") for (int q = 0; q < CQ; q++) {
-            if (!kSweepEarly || mfmap::cap_final(WC, q, false) < 0) *p.s0[q] = back * c0[q];
-            if (!kSweepEarly || mfmap::cap_final(WC, q, true) < 0) *p.s1[q] = back * c1[q];
+            if (mfmap::cap_final(WC, q, false) < 0) *p.s0[q] = back * c0[q];
+            if (mfmap::cap_final(WC, q, true) < 0) *p.s1[q] = back * c1[q];
         }
     }
 #endif
@@ -1460,34 +1282,18 @@ struct WaveQP {
     // S2 body: a_{k+1} = t_{k+1} - F_k a_k for k = 0..W-1 (WC = W, or 0 for a runtime W).
     template <int WC>
     IMPC_WF void fwd_sweep(const double *tb, double *rb, int W) {
-#if IMPC_SWEEP_MFMA_DEV
+#if defined(__HIP_DEVICE_COMPILE__)
         if constexpr (WC > 0) return sweep_mfma<WC, true>(tb, rb);
 #endif
         const double *Fm = lds + LD::F_OFF;
         const int lo = lane_o(), l = lo & 63, i = l >> 3, j = l & 7;  // opaque: see lane_o
         double a = (1.0 / kSweepPre) * tb[i];  // a_0 = t_0 (tb holds t / 8)
-        // (F, t) of the next even / odd step, loaded two steps ahead (reads past the last stage
-        // stay inside the LDS buffers and are never used)
-        double fe = Fm[l], te = tb[13 + j], fo = Fm[64 + l], to = tb[26 + i];
         if constexpr (WC > 0) {
-            double c0[CQ], c1[CQ];
-            _Pragma("unroll") for (int q = 0; q < CQ; q++) c0[q] = c1[q] = 0.0;
-            _Pragma("unroll") for (int k = 0; k < WC; k += 2) {
-                const double f0 = fe, t0 = te;
-                fe = Fm[64 * (k + 2) + l];
-                te = tb[13 * (k + 3) + j];
-                a = rstep<true>(f0, t0, a);
-                capm<true>(c0, a, k, i);
-                if (k + 1 < WC) {
-                    const double f1 = fo, t1 = to;
-                    fo = Fm[64 * (k + 3) + l];
-                    to = tb[13 * (k + 4) + i];
-                    a = rstep<false>(f1, t1, a);
-                    capm<false>(c1, a, k + 1, j);
-                }
-            }
-            cap_store<true>(c0, c1, rb, WC, true, i, j);
+            (void)fwd_run<WC, true>(tb, rb, 0, a);
         } else {
+            // (F, t) of the next even / odd step, loaded two steps ahead (reads past the last stage
+            // stay inside the LDS buffers and are never used)
+            double fe = Fm[l], te = tb[13 + j], fo = Fm[64 + l], to = tb[26 + i];
             // one lane per element writes, the rest write to discard slots (no divergent branch)
             double *junk = lds + LD::JUNK_OFF + lo;
             const bool wri = j == 0, wrj = i == 0;
@@ -1543,7 +1349,7 @@ struct WaveQP {
     // contiguous (even k) reductions; x_k sits at index j (odd k) / i (even k).  WC as above.
     template <bool ODD, int WC>
     IMPC_WF void bwd_sweep(const double *eb, double *xb, int W) {
-#if IMPC_SWEEP_MFMA_DEV
+#if defined(__HIP_DEVICE_COMPILE__)
         if constexpr (WC > 0) return sweep_mfma<WC, false>(eb, xb);
 #endif
         const double *Fm = lds + LD::F_OFF;
@@ -1551,30 +1357,12 @@ struct WaveQP {
         if constexpr (WC > 0) W = WC;
         // x_W = e_W: W = (W-1)+1 has the opposite parity of the first step (eb holds e[:8] / 8)
         double x = (1.0 / kSweepPre) * eb[13 * W + (ODD ? i : j)];
-        const int k1 = W - 2 > 0 ? W - 2 : 0;
-        double fa = Fm[64 * (W - 1) + l], ea = eb[13 * (W - 1) + (ODD ? j : i)];
-        double fb = Fm[64 * k1 + l], ebv = eb[13 * k1 + (ODD ? i : j)];
         if constexpr (WC > 0) {
-            double c0[CQ], c1[CQ];
-            _Pragma("unroll") for (int q = 0; q < CQ; q++) c0[q] = c1[q] = 0.0;
-            _Pragma("unroll") for (int m = 0; m < WC; m += 2) {
-                const int k = WC - 1 - m;
-                const int k2 = k - 2 > 0 ? k - 2 : 0, k3 = k - 3 > 0 ? k - 3 : 0;
-                const double f0 = fa, e0 = ea;
-                fa = Fm[64 * k2 + l];
-                ea = eb[13 * k2 + (ODD ? j : i)];
-                x = rstep<ODD>(f0, e0, x);
-                capm<ODD>(c0, x, m, ODD ? i : j);
-                if (m + 1 < WC) {
-                    const double f1 = fb, e1 = ebv;
-                    fb = Fm[64 * k3 + l];
-                    ebv = eb[13 * k3 + (ODD ? i : j)];
-                    x = rstep<!ODD>(f1, e1, x);
-                    capm<!ODD>(c1, x, m + 1, ODD ? j : i);
-                }
-            }
-            cap_store<ODD>(c0, c1, xb, WC, false, i, j);
+            (void)bwd_run<ODD, WC, true>(eb, xb, 0, x);
         } else {
+            const int k1 = W - 2 > 0 ? W - 2 : 0;
+            double fa = Fm[64 * (W - 1) + l], ea = eb[13 * (W - 1) + (ODD ? j : i)];
+            double fb = Fm[64 * k1 + l], ebv = eb[13 * k1 + (ODD ? i : j)];
             double *junk = lds + LD::JUNK_OFF + lo;
             const bool wri = j == 0, wrj = i == 0;
             for (int k = W - 1; k >= 0; k -= 2) {
@@ -1594,74 +1382,9 @@ struct WaveQP {
         }
     }
 
-    // S2 in chunks (CHUNK; see CH_OFF): steps 0..CL-1 / CL..2CL-1 / 2CL..3CL-1 / 3CL..W-1 on waves
-    // 0..3.  a_2CL = a^_2CL + P1 a_CL, a_3CL = a^_3CL + P2 a^_2CL + P2 P1 a_CL (a^: the chunk run from
-    // zero); chunk starts are even stages, so a_CL sits at index i (captured by wave 0 in rb).
-    IMPC_WF void fwd_chunked(const double *tb, double *rb) {
-        const double *C = chbuf();
-        double *ends = chbuf() + kChEnd;
-        const int w = L >> 6, l = lane_o() & 63, i = l >> 3, j = l & 7;
-        constexpr int A1 = 13 * CL;  // a_CL in rb
-        for (int rep_ = 0; rep_ < (IMPC_CHDUP == 1 ? 2 : 1); rep_++)
-        if (w == 0) {
-            (void)fwd_run<CL, true>(tb, rb, 0, 8.0 * tb[i]);  // a_0 = t_0 (tb holds t / 8)
-        } else if (w == 1) {
-            const double e = fwd_run<CL, false>(tb, rb, CL, 0.0);
-            if (j == 0) ends[i] = e;
-        } else if (w == 2) {
-            const double e = fwd_run<CL, false>(tb, rb, 2 * CL, 0.0);
-            if (j == 0) ends[8 + i] = e;
-        }
-        wv.lsync();
-        for (int rep_ = 0; rep_ < (IMPC_CHDUP == 2 ? 2 : 1); rep_++)
-        if (w == 1) {
-            (void)fwd_run<CL, true>(tb, rb, CL, rb[A1 + i]);
-        } else if (w == 2) {
-            const double a = wv.sum_contig8(__builtin_fma(C[kChFP1 + l], rb[A1 + j], 0.125 * ends[i]));
-            (void)fwd_run<CL, true>(tb, rb, 2 * CL, a);
-        } else if (w == 3) {
-            const double p = __builtin_fma(C[kChFP2 + l], ends[j],
-                                           __builtin_fma(C[kChFP21 + l], rb[A1 + j], 0.125 * ends[8 + i]));
-            (void)fwd_run<CLAST, true>(tb, rb, 3 * CL, wv.sum_contig8(p));
-        }
-    }
-
-    // S4 in chunks: steps W-1..3CL / 3CL-1..2CL / 2CL-1..CL / CL-1..0 on waves 0..3, from x_W /
-    // x_3CL / x_2CL / x_CL (x_2CL = x^_2CL + P1 x_3CL, x_CL = x^_CL + P2 x^_2CL + P2 P1 x_3CL).
-    IMPC_WF void bwd_chunked(const double *eb, double *xb) {
-        const double *C = chbuf();
-        double *ends = chbuf() + kChEnd + kChEnds;
-        const int w = L >> 6, l = lane_o() & 63, i = l >> 3, j = l & 7;
-        constexpr int X3 = 13 * 3 * CL;     // x_3CL in xb (even stage: index i)
-        constexpr bool LODD = (WF - 1) & 1;  // parity of the last chunk's first step W - 1
-        for (int rep_ = 0; rep_ < (IMPC_CHDUP == 1 ? 2 : 1); rep_++)
-        if (w == 0) {
-            // x_W = e_W: at index j for odd W, i for even W
-            (void)bwd_run<LODD, CLAST, true>(eb, xb, 3 * CL, 8.0 * eb[13 * WF + (LODD ? i : j)]);
-        } else if (w == 1) {
-            const double e = bwd_run<true, CL, false>(eb, xb, 2 * CL, 0.0);
-            if (j == 0) ends[i] = e;
-        } else if (w == 2) {
-            const double e = bwd_run<true, CL, false>(eb, xb, CL, 0.0);
-            if (j == 0) ends[8 + i] = e;
-        }
-        wv.lsync();
-        for (int rep_ = 0; rep_ < (IMPC_CHDUP == 2 ? 2 : 1); rep_++)
-        if (w == 1) {
-            (void)bwd_run<true, CL, true>(eb, xb, 2 * CL, xb[X3 + i]);
-        } else if (w == 2) {
-            const double x = wv.sum_contig8(__builtin_fma(C[kChBT1 + l], xb[X3 + j], 0.125 * ends[i]));
-            (void)bwd_run<true, CL, true>(eb, xb, CL, x);
-        } else if (w == 3) {
-            const double p = __builtin_fma(C[kChBT2 + l], ends[j],
-                                           __builtin_fma(C[kChBT21 + l], xb[X3 + j], 0.125 * ends[8 + i]));
-            (void)bwd_run<true, CL, true>(eb, xb, 0, wv.sum_contig8(p));
-        }
-    }
-
-    // S2 in five chunks (NCH = 5): steps c CL .. c CL + CL - 1 (c = 0..3) and 4 CL .. W - 1; waves
+    // S2 in chunks (CHUNK; see CH_OFF): steps c CL .. c CL + CL - 1 (c = 0..3) and 4 CL .. W - 1; waves
     // 1..3 run chunks 1..3 twice, wave 0 chunk 0 in round 1 and chunk 4 in round 2.
-    IMPC_WF void fwd_chunked5(const double *tb, double *rb) {
+    IMPC_WF void fwd_chunked(const double *tb, double *rb) {
         const double *C = chbuf();
         double *ends = chbuf() + kChEnd;
         const int w = L >> 6, l = lane_o() & 63, i = l >> 3, j = l & 7;
@@ -1676,24 +1399,24 @@ struct WaveQP {
         if (w == 1) {
             (void)fwd_run<CL, true>(tb, rb, CL, rb[A1 + i]);
         } else if (w == 2) {
-            const double a = wv.sum_contig8(__builtin_fma(C[kCh5P1 + l], rb[A1 + j], 0.125 * ends[i]));
+            const double a = wv.sum_contig8(__builtin_fma(C[kChP1 + l], rb[A1 + j], 0.125 * ends[i]));
             (void)fwd_run<CL, true>(tb, rb, 2 * CL, a);
         } else if (w == 3) {
-            const double p = __builtin_fma(C[kCh5P2 + l], ends[j],
-                                           __builtin_fma(C[kCh5P21 + l], rb[A1 + j], 0.125 * ends[8 + i]));
+            const double p = __builtin_fma(C[kChP2 + l], ends[j],
+                                           __builtin_fma(C[kChP21 + l], rb[A1 + j], 0.125 * ends[8 + i]));
             (void)fwd_run<CL, true>(tb, rb, 3 * CL, wv.sum_contig8(p));
         } else {
             const double p = __builtin_fma(
-                C[kCh5P3 + l], ends[8 + j],
-                __builtin_fma(C[kCh5P32 + l], ends[j], __builtin_fma(C[kCh5P321 + l], rb[A1 + j], 0.125 * ends[16 + i])));
+                C[kChP3 + l], ends[8 + j],
+                __builtin_fma(C[kChP32 + l], ends[j], __builtin_fma(C[kChP321 + l], rb[A1 + j], 0.125 * ends[16 + i])));
             (void)fwd_run<CLAST, true>(tb, rb, 4 * CL, wv.sum_contig8(p));
         }
     }
 
-    // S4 in five chunks: steps W-1..4CL (wave 0, round 1, from x_W), 4CL-1..3CL / 3CL-1..2CL /
+    // S4 in chunks: steps W-1..4CL (wave 0, round 1, from x_W), 4CL-1..3CL / 3CL-1..2CL /
     // 2CL-1..CL (waves 1..3, both rounds), CL-1..0 (wave 0, round 2).
-    IMPC_WF void bwd_chunked5(const double *eb, double *xb) {
-        const double *C = chbuf() + kCh5B;
+    IMPC_WF void bwd_chunked(const double *eb, double *xb) {
+        const double *C = chbuf() + kChB;
         double *ends = chbuf() + kChEnd + kChEnds;
         const int w = L >> 6, l = lane_o() & 63, i = l >> 3, j = l & 7;
         constexpr int X4 = 13 * 4 * CL;      // x_4CL in xb (even stage: index i)
@@ -1708,16 +1431,16 @@ struct WaveQP {
         if (w == 1) {
             (void)bwd_run<true, CL, true>(eb, xb, 3 * CL, xb[X4 + i]);
         } else if (w == 2) {
-            const double x = wv.sum_contig8(__builtin_fma(C[kCh5P1 + l], xb[X4 + j], 0.125 * ends[i]));
+            const double x = wv.sum_contig8(__builtin_fma(C[kChP1 + l], xb[X4 + j], 0.125 * ends[i]));
             (void)bwd_run<true, CL, true>(eb, xb, 2 * CL, x);
         } else if (w == 3) {
-            const double p = __builtin_fma(C[kCh5P2 + l], ends[j],
-                                           __builtin_fma(C[kCh5P21 + l], xb[X4 + j], 0.125 * ends[8 + i]));
+            const double p = __builtin_fma(C[kChP2 + l], ends[j],
+                                           __builtin_fma(C[kChP21 + l], xb[X4 + j], 0.125 * ends[8 + i]));
             (void)bwd_run<true, CL, true>(eb, xb, CL, wv.sum_contig8(p));
         } else {
             const double p = __builtin_fma(
-                C[kCh5P3 + l], ends[8 + j],
-                __builtin_fma(C[kCh5P32 + l], ends[j], __builtin_fma(C[kCh5P321 + l], xb[X4 + j], 0.125 * ends[16 + i])));
+                C[kChP3 + l], ends[8 + j],
+                __builtin_fma(C[kChP32 + l], ends[j], __builtin_fma(C[kChP321 + l], xb[X4 + j], 0.125 * ends[16 + i])));
             (void)bwd_run<true, CL, true>(eb, xb, 0, wv.sum_contig8(p));
         }
     }
@@ -1739,8 +1462,8 @@ struct WaveQP {
         double *rb = rbuf(), *tb = tbuf(), *eb = ebuf(), *xb = xbuf();
         const double sigma = sig_;
         const bool sweeper = (L >> 6) == rw;
-#if IMPC_SWEEP_MFMA_DEV
-        // kSweepPro: each sweep's prologue, formed by its wavefront in front of the releasing barrier
+#if defined(__HIP_DEVICE_COMPILE__)
+        // kSweep19: each sweep's prologue, formed by its wavefront in front of the releasing barrier
         [[maybe_unused]] SweepPro fpro, bpro;
 #endif
         IMPC_REP(kSecRhs) {
@@ -1773,8 +1496,8 @@ struct WaveQP {
                 _Pragma("unroll") for (int cc = 0; cc < 5; cc++) t -= cp[s][cc] * rv[cc];
                 tb[v] = kSweepPre * t;  // the forward sweep's input, pre-scaled (rstep)
             }
-#if IMPC_SWEEP_MFMA_DEV
-            if constexpr (kSweepPro) {
+#if defined(__HIP_DEVICE_COMPILE__)
+            if constexpr (kSweep19) {
                 if (sweeper && W == LD::WSPEC) {
                     sweep_pro<LD::WSPEC, true>(fpro, rb);
                 }
@@ -1793,15 +1516,13 @@ struct WaveQP {
             // leave their SIMD's issue slots to the co-resident team.
             // (a_0 = t_0 = r_0[:8] is already in rb: stage 0 has no coupling, so S1 left it as is)
             // The long horizon's W = 39 instance runs it in chunks on all four wavefronts (CHUNK).
-            if constexpr (CHUNK && NCH == 5) {
-                fwd_chunked5(tb, rb);
-            } else if constexpr (CHUNK) {
+            if constexpr (CHUNK) {
                 fwd_chunked(tb, rb);
             } else if (sweeper) {
                 IMPC_PRIO_UP();
                 if (W == LD::WSPEC) {
-#if IMPC_SWEEP_MFMA_DEV
-                    if constexpr (kSweepPro) sweep_run<LD::WSPEC, true>(fpro, tb); else
+#if defined(__HIP_DEVICE_COMPILE__)
+                    if constexpr (kSweep19) sweep_run<LD::WSPEC, true>(fpro, tb); else
 #endif
                     fwd_sweep<LD::WSPEC>(tb, rb, W);
                 } else
@@ -1823,8 +1544,8 @@ struct WaveQP {
                 // the state part pre-scaled for the backward sweep (rstep); S5 reads the controls' e
                 eb[NL * s + L] = vr_[s] < 8 ? kSweepPre * e : e;
             }
-#if IMPC_SWEEP_MFMA_DEV
-            if constexpr (kSweepPro) {
+#if defined(__HIP_DEVICE_COMPILE__)
+            if constexpr (kSweep19) {
                 if (sweeper && W == LD::WSPEC) {
                     sweep_pro<LD::WSPEC, false>(bpro, xb);
                 }
@@ -1837,15 +1558,13 @@ struct WaveQP {
             // S4: backward 8-dim recursion x_k[:8] = e_k[:8] - F_k' x_{k+1}[:8] on the same grid and
             // stored layout: even steps reduce over j (contiguous), odd steps over i (strided).
             if (L < 8) xb[13 * W + L] = (1.0 / kSweepPre) * eb[13 * W + L];
-            if constexpr (CHUNK && NCH == 5) {
-                bwd_chunked5(eb, xb);
-            } else if constexpr (CHUNK) {
+            if constexpr (CHUNK) {
                 bwd_chunked(eb, xb);
             } else if (sweeper) {
                 IMPC_PRIO_UP();
                 if (W == LD::WSPEC) {
-#if IMPC_SWEEP_MFMA_DEV
-                    if constexpr (kSweepPro) sweep_run<LD::WSPEC, false>(bpro, eb); else
+#if defined(__HIP_DEVICE_COMPILE__)
+                    if constexpr (kSweep19) sweep_run<LD::WSPEC, false>(bpro, eb); else
 #endif
                     bwd_sweep<((LD::WSPEC - 1) & 1) != 0, LD::WSPEC>(eb, xb, W);
                 } else if ((W - 1) & 1)
@@ -2077,7 +1796,6 @@ struct WaveQP {
         const bool unsc = st.scaling > 0 && !st.scaled_termination;
         int res = 0;
         if (nrm > kDivTol && lhs < eps * nrm) {
-            IMPC_COUNT(0);
             double *pb = pbuf();
             _Pragma("unroll") for (int s = 0; s < GS; s++) {
                 if (gok[s]) {
@@ -2121,9 +1839,7 @@ struct WaveQP {
         const double cs = unsc ? c : 1.0;
         int res = 0;
         if (nrm > kDivTol && qdx < cs * eps * nrm) {
-            IMPC_COUNT(1);
             if (mx < cs * eps * nrm) {
-                IMPC_COUNT(2);
                 double *xb = xbuf();
                 _Pragma("unroll") for (int s = 0; s < VS; s++)
                     if (vok[s]) xb[NL * s + L] = dxv(s);
@@ -2171,9 +1887,6 @@ struct WaveQP {
         prim_ok = !ptest;
         dual_ok = inf.dua_res < eps_abs + eps_rel * inf.dua_norm_u;
         // the first stages' norms and sums were reduced with the residual norms (update_info)
-        IMPC_COUNT(3);
-        if (ptest) IMPC_COUNT(4);
-        if (!dual_ok) IMPC_COUNT(5);
         if (ptest) prim_inf = pinf_stage2(eps_pinf, inf.pinf_nrm, inf.pinf_lhs, D);
         if (!dual_ok) dual_inf = dinf_stage2(eps_dinf, inf.dinf_nrm, inf.dinf_qdx, inf.dinf_pdx, Eb, Eg);
         if (prim_ok && dual_ok) {
