@@ -35,6 +35,7 @@ EMU64   := $(HARNDIR)/libwave_emu64.so
 SHIMT   := $(HARNDIR)/shim_test
 REPLANX := $(HARNDIR)/replan_example
 DETECTH := $(HARNDIR)/libdetect_harness.so
+EXECH   := $(HARNDIR)/libexec_harness.so
 MFMODEL := $(HARNDIR)/sweep_mfma_model
 STMODEL := $(HARNDIR)/sweep_store_model
 
@@ -42,7 +43,7 @@ STMODEL := $(HARNDIR)/sweep_store_model
 all: lib oracle harness
 lib: $(LIB)
 oracle: $(ORACLE)
-harness: $(HARNESS) $(EMU) $(EMU64) $(SHIMT) $(REPLANX) $(DETECTH) $(MFMODEL) $(STMODEL)
+harness: $(HARNESS) $(EMU) $(EMU64) $(SHIMT) $(REPLANX) $(DETECTH) $(EXECH) $(MFMODEL) $(STMODEL)
 
 # (every source and header of the library: the build identity above is taken over the same list)
 $(LIBDIR)/impc_qp.o: $(CSRC)/impc_qp.hip $(SRCS)
@@ -61,7 +62,7 @@ $(PROFLIB): $(LIBDIR)/impc_qp_prof.o $(LIBDIR)/replan_run.o $(LIBDIR)/symbolic.o
 # kernels over the library's own entry points
 $(LIBDIR)/replan_run.o: $(CSRC)/replan_run.hip $(CSRC)/lib_internal.hpp $(ROOT)/include/impc_replan.h \
 		$(ROOT)/include/impc_qp.h $(ROOT)/include/impc_mpc.h $(ROOT)/include/impc_fanout.h $(ROOT)/include/impc_select.h \
-		$(ROOT)/include/impc_comm.h
+		$(ROOT)/include/impc_comm.h $(ROOT)/include/impc_exec.h $(ROOT)/include/impc_predict.h $(CSRC)/plan_exec.hpp
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -121,6 +122,12 @@ $(REPLANX): $(ROOT)/tests/native/replan_example.cpp $(ROOT)/include/impc_qp.h $(
 
 # the range gate's predicate (csrc/detect_gate.hpp) compiled for the host
 $(DETECTH): $(ROOT)/tests/native/detect_harness.cpp $(CSRC)/detect_gate.hpp
+	@mkdir -p $(HARNDIR)
+	$(HIPCC) -x hip --offload-host-only -std=c++17 -O2 -fPIC -shared -ffp-contract=off $< -o $@
+
+# the plan getters, tracking target and collision tests (csrc/plan_exec.hpp) compiled for the host
+$(EXECH): $(ROOT)/tests/native/exec_harness.cpp $(CSRC)/plan_exec.hpp $(ROOT)/include/impc_exec.h \
+		$(ROOT)/include/impc_replan.h $(ROOT)/include/impc_predict.h
 	@mkdir -p $(HARNDIR)
 	$(HIPCC) -x hip --offload-host-only -std=c++17 -O2 -fPIC -shared -ffp-contract=off $< -o $@
 

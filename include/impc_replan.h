@@ -141,6 +141,11 @@ typedef struct {
                                                       is queued, not waited for */
 } impc_replan_stats;
 
+/* The grouped solve runs on the structured kernel only.  A configuration whose QPs it does not take
+ * (13 N - 5 variables beyond its 768, or obstacle rows beyond its LDS) still gives an object: it
+ * holds the planner state -- impc_replan_set_state / _set_ref, the views, impc_replan_advance_device
+ * and the plan-execution calls of impc_exec.h serve plans of any horizon -- and impc_replan_run and
+ * impc_replan_shape return IMPC_UNSUPPORTED. */
 int impc_replan_create(impc_ctx ctx, const impc_replan_config *cfg, impc_replan *out);
 int impc_replan_destroy(impc_replan rp);
 /* The planner state from the host: plan_x [I][n] (currentStatesSol_ then currentControlsSol_ in
@@ -174,6 +179,19 @@ typedef struct {
     double *weighted;
 } impc_replan_view;
 int impc_replan_view_device(impc_replan rp, impc_replan_view *out);
+
+/* ref_, the reference the reference commits with every plan (mpcPlanner.cpp:566, :639, :657) and
+ * getRef interpolates (:1309-1324): plan_ref [I][N][3], rows 0..2 of the xref of the instance's last
+ * valid replan, and ref_count [I] = ref_.size(), N once a reference was committed and 0 before
+ * (getRef then returns currPos_, :1310-1312).  impc_replan_run copies them after the commit for the
+ * instances with valid = 1 (others keep theirs); impc_replan_set_state sets every ref_count to 0.
+ * impc_replan_set_ref restores a state from the host (ref [I][N][3]; synchronous, like
+ * impc_replan_set_state, after which it is called): ref_count becomes N for every instance that
+ * holds a plan (prev_count > 0) and 0 for the others.  impc_replan_ref_device returns the DEVICE
+ * views (either output may be NULL), valid until destroy.  (Not part of impc_replan_view, whose
+ * layout is fixed.) */
+int impc_replan_set_ref(impc_replan rp, const double *ref);
+int impc_replan_ref_device(impc_replan rp, double **plan_ref, int32_t **ref_count);
 
 /* Inspection of the last run (tests, tools; synchronises the context): shape k = the QPs with k
  * dynamic-obstacle rows per stage (0 <= k <= K + 1; k = K + 2: the first plans of a replan object

@@ -22,6 +22,7 @@
 //   k_cand        the candidates' validity (solveProblem NoError), solution pointers, obstacle sets
 //   selection     impc_select_best_device over every instance (non-fan-out instances: no candidate)
 //   k_commit      every plan into the planner state
+//   k_commit_ref   the reference of every committed plan (ref_, plan_exec.hpp)
 //
 // No x, y, QP value or count leaves the device, and nothing on the host waits for it.
 #include <hip/hip_runtime.h>
@@ -33,12 +34,14 @@
 #include <string>
 #include <vector>
 
+#include "../../include/impc_exec.h"
 #include "../../include/impc_fanout.h"
 #include "../../include/impc_mpc.h"
 #include "../../include/impc_qp.h"
 #include "../../include/impc_replan.h"
 #include "../../include/impc_select.h"
 #include "lib_internal.hpp"
+#include "plan_exec.hpp"
 
 #define RP_HIP(expr)                                                                                        \
     do {                                                                                                    \
@@ -589,6 +592,9 @@ struct impc_replan_s {
     double *plan_x = nullptr, *plan_states = nullptr;
     int32_t *prev_count = nullptr;
     int8_t *first_time = nullptr, *valid = nullptr, *zeros8 = nullptr;
+    double *plan_ref = nullptr;     // ref_ [I][N][3]
+    int32_t *ref_count = nullptr;   // ref_.size() [I]
+    bool has_state = false;         // a state from the caller (impc_replan_set_state) or a run
     // rows of the shapes and per-instance outputs
     int8_t *branch = nullptr, *row_code = nullptr;
     int32_t *row_inst = nullptr, *num_obs = nullptr, *shp = nullptr, *slot_row = nullptr, *slot_type = nullptr;
@@ -615,7 +621,8 @@ namespace {
 
 int fail(int code, const char *msg) { return impc_lib::set_error(code, msg); }
 
-int make_shape(impc_replan rp, Shape &s, int32_t k, int32_t nst, int64_t cap) {
+// *no_kernel: the pattern is not one the structured kernel takes (the only kernel of the grouped solve)
+int make_shape(impc_replan rp, Shape &s, int32_t k, int32_t nst, int64_t cap, bool *no_kernel) {
     s.k = k, s.nst = nst, s.cap = cap;
     RP_TRY(impc_mpc_dims(&rp->cfg.mpc, nst, k, &s.dm));
     std::vector<int64_t> Pp(s.dm.n + 1), Pi(std::max<int64_t>(s.dm.nnzP, 1)), Ap(s.dm.n + 1), Ai(s.dm.nnzA);
@@ -627,7 +634,10 @@ int make_shape(impc_replan rp, Shape &s, int32_t k, int32_t nst, int64_t cap) {
         const double qw = 1.0 / (10.0 * (rp->N - 1) * rp->cfg.mpc.position_weight);
         RP_TRY(impc_batch_set_queue_order(s.batch, IMPC_QUEUE_LONGEST_FIRST, qw));
     }
-    RP_TRY(impc_batch_set_kernel(s.batch, IMPC_KERNEL_STRUCTURED));
+    if (int rc = impc_batch_set_kernel(s.batch, IMPC_KERNEL_STRUCTURED)) {
+        *no_kernel = rc == IMPC_UNSUPPORTED;
+        return rc;
+    }
     RP_TRY(impc_mpc_builder_create(rp->ctx, &rp->cfg.mpc, nst, k, rp->L, &s.bld));
     impc_lib::BatchInputs bi{};
     RP_TRY(impc_lib::batch_inputs_view(s.batch, &bi));
@@ -696,6 +706,8 @@ int impc_replan_create(impc_ctx ctx, const impc_replan_config *cfg, impc_replan 
     RP_CK(a.get((size_t)I, &rp->first_time));
     RP_CK(a.get((size_t)I, &rp->valid));
     RP_CK(a.get((size_t)I, &rp->zeros8));
+    RP_CK(a.get((size_t)(I * N * 3), &rp->plan_ref));
+    RP_CK(a.get((size_t)I, &rp->ref_count));
     RP_CK(a.get((size_t)I, &rp->branch));
     RP_CK(a.get((size_t)rp->rows, &rp->row_inst));
     RP_CK(a.get((size_t)rp->rows, &rp->row_code));
@@ -724,6 +736,7 @@ int impc_replan_create(impc_ctx ctx, const impc_replan_config *cfg, impc_replan 
     hipStream_t st = impc_lib::stream(ctx);
     if (hipMemsetAsync(rp->zeros8, 0, (size_t)I, st) != hipSuccess ||
         hipMemsetAsync(rp->valid, 0, (size_t)I, st) != hipSuccess ||
+        hipMemsetAsync(rp->plan_ref, 0, sizeof(double) * (size_t)(I * N * 3), st) != hipSuccess ||
         hipMemsetAsync(rp->cnt, 0, sizeof(int64_t) * (size_t)(2 * S + 3), st) != hipSuccess ||
         hipMemsetAsync(rp->solve, 0, sizeof(int64_t) * (size_t)S, st) != hipSuccess) {
         cleanup();
@@ -734,12 +747,28 @@ int impc_replan_create(impc_ctx ctx, const impc_replan_config *cfg, impc_replan 
     std::vector<ShapeDev> hdev((size_t)S);
     for (int32_t k = 0; k < S; k++) {
         Shape &s = rp->sh[(size_t)k];
-        RP_CK(make_shape(rp.get(), s, shape_dyn(K, k), k <= K + 1 ? rp->nst : 0, shape_cap(I, K, k)));
+        bool no_kernel = false;
+        rc = make_shape(rp.get(), s, shape_dyn(K, k), k <= K + 1 ? rp->nst : 0, shape_cap(I, K, k), &no_kernel);
+        if (rc && no_kernel) {
+            // A horizon or obstacle count beyond the structured kernel (13 N - 5 variables over its
+            // lanes, or its LDS): the object holds the planner state -- set_state, set_ref, the records'
+            // views, the plan-execution calls of impc_exec.h -- and impc_replan_run is unsupported.
+            for (Shape &d : rp->sh) free_shape(d);
+            rp->sh.clear();
+            rp->group.clear();
+            rc = IMPC_OK;
+            break;
+        }
+        if (rc) {
+            cleanup();
+            return rc;
+        }
         RP_CK(impc_lib::batch_set_active_device(s.batch, rp->solve + k));
         hdev[(size_t)k] = s.dev;
         rp->group.push_back(s.batch);
     }
-    RP_CK(impc_copy_to_device(ctx, rp->d_sh, hdev.data(), (int64_t)(sizeof(ShapeDev) * hdev.size())));
+    if (!rp->sh.empty())
+        RP_CK(impc_copy_to_device(ctx, rp->d_sh, hdev.data(), (int64_t)(sizeof(ShapeDev) * hdev.size())));
     {  // the row scan's counters: (2 S + 3) x (lanes + wave totals) int32 of LDS
         const size_t lds = sizeof(int32_t) * (size_t)(2 * S + 3) * (kPlanLanes + kPlanLanes / 64);
         if (lds > 64 * 1024 &&
@@ -755,6 +784,7 @@ int impc_replan_create(impc_ctx ctx, const impc_replan_config *cfg, impc_replan 
         cleanup();
         return rc;
     }
+    rp->has_state = false;
     *out = rp.release();
     return IMPC_OK;
 }
@@ -786,6 +816,25 @@ int impc_replan_set_state(impc_replan rp, const double *plan_x, const int8_t *fi
     RP_TRY(impc_copy_to_device(rp->ctx, rp->first_time, ft.data(), I));
     RP_TRY(impc_copy_to_device(rp->ctx, rp->prev_count, pc.data(), 4 * I));
     RP_TRY(impc_copy_to_device(rp->ctx, rp->valid, v.data(), I));
+    std::vector<int32_t> rc((size_t)I, 0);  // ref_.empty()
+    RP_TRY(impc_copy_to_device(rp->ctx, rp->ref_count, rc.data(), 4 * I));
+    rp->has_state = true;
+    return IMPC_OK;
+}
+
+int impc_replan_set_ref(impc_replan rp, const double *ref) {
+    if (!rp || !ref) return fail(IMPC_INVALID_ARGUMENT, "replan set_ref: null object or ref");
+    RP_TRY(impc_copy_to_device(rp->ctx, rp->plan_ref, ref, (int64_t)sizeof(double) * rp->I * rp->N * 3));
+    hipLaunchKernelGGL(impc_exec::k_ref_count, dim3(grid_for(rp, rp->I)), dim3(256), 0, impc_lib::stream(rp->ctx), rp->I,
+                       rp->N, rp->prev_count, rp->ref_count);
+    RP_HIP(hipGetLastError());
+    return impc_ctx_synchronize(rp->ctx);
+}
+
+int impc_replan_ref_device(impc_replan rp, double **plan_ref, int32_t **ref_count) {
+    if (!rp) return fail(IMPC_INVALID_ARGUMENT, "null replan");
+    if (plan_ref) *plan_ref = rp->plan_ref;
+    if (ref_count) *ref_count = rp->ref_count;
     return IMPC_OK;
 }
 
@@ -798,6 +847,9 @@ int impc_replan_run(impc_replan rp, const impc_replan_inputs *in) {
     if (in->cur_count && !in->cur_size) return fail(IMPC_INVALID_ARGUMENT, "replan: cur_count needs cur_size");
     if (rp->nst > 0 && (!in->st_centroid || !in->st_size || !in->st_yaw))
         return fail(IMPC_INVALID_ARGUMENT, "replan: num_static > 0 needs st_centroid, st_size, st_yaw");
+    if (rp->sh.empty())
+        return fail(IMPC_UNSUPPORTED, "replan: the horizon / obstacle count is beyond the structured kernel "
+                                      "(the object only holds plan state)");
     impc_ctx ctx = rp->ctx;
     RP_HIP(hipSetDevice(impc_lib::device(ctx)));
     hipStream_t st = impc_lib::stream(ctx);
@@ -871,7 +923,12 @@ int impc_replan_run(impc_replan rp, const impc_replan_inputs *in) {
                   rp->plan_states, rp->prev_count, rp->first_time, rp->valid};
     hipLaunchKernelGGL(k_commit, dim3(grid_for(rp, I, 1)), dim3(64), 0, st, cm);
     RP_HIP(hipGetLastError());
+    // ---- ref_ of every committed plan (:639 / :657)
+    hipLaunchKernelGGL(impc_exec::k_commit_ref, dim3(grid_for(rp, I * N * 3)), dim3(256), 0, st, I, N, rp->valid,
+                       in->xref, rp->plan_ref, rp->ref_count);
+    RP_HIP(hipGetLastError());
     rp->ran = true;
+    rp->has_state = true;
     rp->last_limit = tl;
     rp->last_total_s = std::chrono::duration<double>(clk::now() - t_entry).count();
     return IMPC_OK;
@@ -914,6 +971,7 @@ int impc_replan_shape(impc_replan rp, int32_t obstacles, impc_batch *batch, int6
                       const double **l, const double **u) {
     if (!rp || obstacles < 0 || obstacles >= rp->S)
         return fail(IMPC_INVALID_ARGUMENT, "replan: shape must be in 0 .. num_obstacles + 1 (+ 2 with num_static)");
+    if (rp->sh.empty()) return fail(IMPC_UNSUPPORTED, "replan: no solver shapes (the object only holds plan state)");
     const Shape &s = rp->sh[(size_t)obstacles];
     int64_t c = 0;
     if (rp->ran) {
@@ -990,6 +1048,55 @@ int impc_replan_advance_device(impc_replan rp, double t, double *pos, double *ve
     RP_HIP(hipSetDevice(impc_lib::device(rp->ctx)));
     hipLaunchKernelGGL(k_advance, dim3(grid_for(rp, rp->I)), dim3(256), 0, impc_lib::stream(rp->ctx), rp->I, rp->N,
                        rp->n, rp->cfg.mpc.ts, t, rp->valid, rp->plan_x, pos, vel);
+    RP_HIP(hipGetLastError());
+    return IMPC_OK;
+}
+
+namespace {
+
+int exec_state(impc_replan rp, impc_exec::State *s) {
+    if (!rp->has_state)
+        return fail(IMPC_INVALID_ARGUMENT, "replan: no plan state yet (impc_replan_set_state or impc_replan_run first)");
+    if (!(rp->cfg.mpc.ts > 0.0)) return fail(IMPC_INVALID_ARGUMENT, "replan: mpc.ts must be positive");
+    *s = impc_exec::State{rp->I, rp->n, rp->N, rp->K, rp->cfg.mpc.ts, rp->plan_x, rp->plan_ref, rp->prev_count,
+                          rp->ref_count};
+    return IMPC_OK;
+}
+
+}  // namespace
+
+int impc_replan_target_device(impc_replan rp, const impc_target_params *p, const impc_target_in *in,
+                              const impc_target_out *out) {
+    if (!rp || !p || !in || !out) return fail(IMPC_INVALID_ARGUMENT, "replan target: null object, params, in or out");
+    if (!in->t || !in->cur_pos || !in->odom_yaw || !out->pos || !out->vel || !out->acc || !out->yaw || !out->done)
+        return fail(IMPC_INVALID_ARGUMENT, "replan target: t, cur_pos, odom_yaw, pos, vel, acc, yaw, done are required");
+    if (p->yaw_mode < IMPC_YAW_FACING || p->yaw_mode > IMPC_YAW_SMOOTH)
+        return fail(IMPC_INVALID_ARGUMENT, "replan target: unknown yaw_mode");
+    if (p->yaw_mode == IMPC_YAW_FACING && !in->facing_yaw)
+        return fail(IMPC_INVALID_ARGUMENT, "replan target: IMPC_YAW_FACING needs facing_yaw");
+    impc_exec::State s{};
+    RP_TRY(exec_state(rp, &s));
+    RP_HIP(hipSetDevice(impc_lib::device(rp->ctx)));
+    hipLaunchKernelGGL(impc_exec::k_target, dim3(grid_for(rp, rp->I, 1)), dim3(64), 0, impc_lib::stream(rp->ctx), s, *p,
+                       *in, *out);
+    RP_HIP(hipGetLastError());
+    return IMPC_OK;
+}
+
+int impc_replan_check_device(impc_replan rp, const impc_check_in *in, const impc_check_out *out) {
+    if (!rp || !in || !out) return fail(IMPC_INVALID_ARGUMENT, "replan check: null object, in or out");
+    if (!in->t || !in->cur_pos || !out->map_step || !out->dyn_step || !out->replan)
+        return fail(IMPC_INVALID_ARGUMENT, "replan check: t, cur_pos, map_step, dyn_step, replan are required");
+    if (in->num_obs && (!in->ob_pos || !in->ob_size))
+        return fail(IMPC_INVALID_ARGUMENT, "replan check: num_obs needs ob_pos and ob_size");
+    if (in->occ_inflated &&
+        (!(in->map.resolution > 0.0) || in->map.dims[0] < 1 || in->map.dims[1] < 1 || in->map.dims[2] < 1))
+        return fail(IMPC_INVALID_ARGUMENT, "replan check: the map needs a positive resolution and dimensions");
+    impc_exec::State s{};
+    RP_TRY(exec_state(rp, &s));
+    RP_HIP(hipSetDevice(impc_lib::device(rp->ctx)));
+    hipLaunchKernelGGL(impc_exec::k_check, dim3(grid_for(rp, rp->I, 1)), dim3(64), 0, impc_lib::stream(rp->ctx), s, *in,
+                       *out);
     RP_HIP(hipGetLastError());
     return IMPC_OK;
 }

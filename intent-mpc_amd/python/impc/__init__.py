@@ -266,7 +266,8 @@ EXPORTED = [
     "impc_batch_update_lin_cost_device", "impc_batch_update_bounds_device", "impc_ctx_pool_stats",
     "impc_replan_create", "impc_replan_destroy", "impc_replan_set_state", "impc_replan_run", "impc_replan_get_stats",
     "impc_replan_view_device", "impc_replan_shape", "impc_replan_advance_device", "impc_batch_follow_plan_device",
-    "impc_replan_pack_device", "impc_replan_gather",  # bound in impc.replan
+    "impc_replan_pack_device", "impc_replan_gather", "impc_replan_set_ref", "impc_replan_ref_device",  # bound in impc.replan
+    "impc_replan_target_device", "impc_replan_check_device",  # bound in impc.execution
     "impc_copy_rows_device", "impc_batch_update_matrices", "impc_batch_update_matrices_device",
     "impc_batch_get_persistent", "impc_batch_get_occupancy",
     "impc_tracks_create", "impc_tracks_destroy", "impc_tracks_push_device", "impc_tracks_reset",

@@ -168,8 +168,10 @@ class DeviceTick:
     with num_pred = the gate's K_i.  predictor=False is the use_predictor: false path
     (mpcNavigation.cpp:301-311, :705-716: getObstaclesInSensorRange -> updateDynamicObstacles): the
     replan gets the gate's cur_pos / cur_size / num as dyn_cur / cur_size / cur_count and has_pred all
-    zero, its SINGLE_CURRENT branch.  Owns the gate's and the predictor's output buffers; `replan`
-    is an impc.replan.DeviceReplan with K = params.max_out slots."""
+    zero, its SINGLE_CURRENT branch.  After the plan, target() and check() serve what the caller does
+    with it (impc.execution: trajExeCB's tracking target, and mpcHasCollision / hasDynamicCollision
+    against the tick's map and the gate's boxes), on the same stream.  Owns the gate's and the
+    predictor's output buffers; `replan` is an impc.replan.DeviceReplan with K = params.max_out slots."""
 
     def __init__(self, ctx, replan, tracks, params, occ=None, omap=None, tp=None, ip=None, predictor=True):
         I, K, L = replan.I, replan.K, replan.L
@@ -185,16 +187,17 @@ class DeviceTick:
         self.pred_size = DeviceArray(ctx, np.zeros((I, K, 4, L, 3)))
         self.prob = DeviceArray(ctx, np.full((I, K, 4), 0.25))
         self.no_pred = DeviceArray(ctx, np.zeros(I, np.int8))
-        self._own_occ = None
-        if self.predictor:
-            if omap is None or occ is None:
-                raise ValueError("DeviceTick: the predictor needs the occupancy map (omap, occ)")
+        self._own_occ = self.omap = self.occ_ptr = self.check_out = None
+        if self.predictor and (omap is None or occ is None):
+            raise ValueError("DeviceTick: the predictor needs the occupancy map (omap, occ)")
+        if omap is not None and occ is not None:  # the predictor's map, and check()'s
             self.omap = omap if isinstance(omap, OccMap) else occ_map(omap["origin"], omap["res"], omap["dims"])
             if isinstance(occ, np.ndarray):
                 self._own_occ = DeviceArray(ctx, np.ascontiguousarray(occ, np.uint8).reshape(-1))
                 self.occ_ptr = self._own_occ.ptr
             else:
                 self.occ_ptr = int(occ)
+        if self.predictor:
             self.tp = tp if tp is not None else traj_params(L - 1, dt=replan.pd["ts"])
             if self.tp.num_pred != L - 1:
                 raise ValueError("DeviceTick: the predictor's num_pred must be the replan's pred_len - 1")
@@ -238,8 +241,34 @@ class DeviceTick:
             self.predict()
         self.plan(pos_ptr, vel_ptr, xref_ptr, **kw)
 
+    def target(self, yaw_mode, t_ptr, pos_ptr, odom_yaw_ptr, out, ready_ptr=None, facing_yaw_ptr=None,
+               forward_dist=1.0):
+        """trajExeCB of every vehicle on its committed plan (impc_replan_target_device): t [I]
+        (realTime), pos [I][3] (currPos_), odom_yaw [I]; out: the output addresses by name (pos, vel,
+        acc, yaw, done, optionally ref, yaw_step -- impc.execution.TargetBuffers.ptrs())."""
+        from . import execution as E
+        E.target_device(self.replan, yaw_mode, t_ptr, pos_ptr, odom_yaw_ptr, ready=ready_ptr,
+                        facing_yaw=facing_yaw_ptr, forward_dist=forward_dist, **out)
+
+    def check(self, t_ptr, pos_ptr, ready_ptr=None):
+        """The "replan now" tests of every vehicle (impc_replan_check_device): mpcHasCollision against
+        the tick's own map (skipped without one) and hasDynamicCollision against the gate's boxes of
+        the last gather (num / cur_pos / cur_size: getObstaclesInSensorRange, mpcNavigation.cpp:705-716).
+        t [I] (realTime), pos [I][3] (currPos_).  Returns the tick's impc.execution.CheckBuffers
+        (map_step, dyn_step, replan_flag on the device; allocated at the first call)."""
+        from . import execution as E
+        g = self.gate
+        if self.check_out is None:
+            self.check_out = E.CheckBuffers(self.ctx, self.I)
+        E.check_device(self.replan, t_ptr, pos_ptr, ready=ready_ptr, omap=self.omap, occ=self.occ_ptr,
+                       num_obs=g.num.ptr, ob_pos=g.cur_pos.ptr, ob_size=g.cur_size.ptr, **self.check_out.ptrs())
+        return self.check_out
+
     def close(self):
         self.gate.free()
+        if self.check_out is not None:
+            self.check_out.free()
+            self.check_out = None
         for d in (self.pred_pos, self.pred_size, self.prob, self.no_pred, self._own_occ):
             if d is not None:
                 d.free()

@@ -121,6 +121,8 @@ _sig("impc_replan_run", _P, C.POINTER(ReplanInputs))
 _sig("impc_replan_get_stats", _P, C.POINTER(ReplanStats))
 _sig("impc_replan_view_device", _P, C.POINTER(ReplanView))
 _sig("impc_replan_advance_device", _P, C.c_double, _P, _P)
+_sig("impc_replan_set_ref", _P, _P)
+_sig("impc_replan_ref_device", _P, C.POINTER(_P), C.POINTER(_P))
 _sig("impc_replan_pack_device", _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64, _P)
 _sig("impc_replan_gather", _P, _P, C.c_int64, C.c_int32, C.c_int64, _P)
 _sig("impc_replan_shape", _P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P),
@@ -239,6 +241,23 @@ class DeviceReplan:
         _check(lib.impc_replan_set_state(self.h, None if px is None else px.ctypes.data_as(_P),
                                          None if ft is None else ft.ctypes.data_as(_P)), "impc_replan_set_state")
         self.first_time_h = np.ones(self.I, np.int8) if ft is None else ft.copy()
+
+    def set_ref(self, ref):
+        """impc_replan_set_ref from a host array ref [I][N][3] (ref_, rows 0..2 of the committed xref):
+        after set_state; ref_count becomes N for every instance that holds a plan."""
+        r = np.ascontiguousarray(ref, np.float64).reshape(self.I, self.N, 3)
+        _check(lib.impc_replan_set_ref(self.h, r.ctypes.data_as(_P)), "impc_replan_set_ref")
+
+    def ref_device(self):
+        """impc_replan_ref_device: the device addresses (plan_ref [I][N][3], ref_count [I] int32)."""
+        pr, rc = _P(), _P()
+        _check(lib.impc_replan_ref_device(self.h, C.byref(pr), C.byref(rc)), "impc_replan_ref_device")
+        return pr.value, rc.value
+
+    def refs(self):
+        """(plan_ref [I][N][3], ref_count [I]) on the host."""
+        pr, rc = self.ref_device()
+        return _get(self.ctx, pr, (self.I, self.N, 3), np.float64), _get(self.ctx, rc, self.I, np.int32)
 
     def view(self):
         v = ReplanView()

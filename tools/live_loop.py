@@ -36,7 +36,10 @@ intent probabilities -> predicted trajectories -> makePlanWithPred with num_pred
 and the vehicle following its plan, all queued on the context stream.  K_i changes only when an
 obstacle crosses the sensor range.  The line gains, per replan, the histogram of K_i, the count of
 truncated instances (more in range than the K slots), the branch counts and the device times of the
-gate, the two predictor kernels and the replan (the context's step timer).  One GPU.  The same tick
+gate, the two predictor kernels and the replan (the context's step timer), and how many vehicles raised
+`replan` (impc_replan_check_device on the fresh plan, the tick's map and the gate's boxes) and how
+many were `done` (impc_replan_target_device one replan period into it); the two counts are also
+printed per replan on stderr.  One GPU.  The same tick
 at small I is checked replan by replan in tests/test_tick.py."""
 import argparse
 import json
@@ -64,6 +67,7 @@ def relaunch(n, argv):
 
 def detector_loop(a):
     import impc
+    from impc import execution as E
     from impc import perception as P
     from impc import scenarios
     from impc.replan import DeviceReplan
@@ -83,7 +87,11 @@ def detector_loop(a):
     pos_d, vel_d, xref_d = Dv(ctx, c(w["pos0"])), Dv(ctx, c(w["vel0"])), Dv(ctx, (I, N, 8))
     world_d, wvel_d, wsize_d = Dv(ctx, c(w["world_pos"])), Dv(ctx, c(w["world_vel"])), Dv(ctx, c(w["world_size"]))
     step = world_d.nbytes // (R * PUSHES)
-    walls, branches, k_hist, truncated = [], [], [], []
+    # what the caller does with each plan (impc.execution): the tracking target one replan period into
+    # it and the "replan now" tests at its start, queued behind the replan
+    t_target, t_check, yaw_d = Dv(ctx, np.full(I, pd["ts"])), Dv(ctx, np.zeros(I)), Dv(ctx, np.zeros(I))
+    tgt = E.TargetBuffers(ctx, I)
+    walls, branches, k_hist, truncated, raised, done = [], [], [], [], [], []
     for r in range(R):
         ctx.synchronize()
         t = time.perf_counter()
@@ -102,9 +110,14 @@ def detector_loop(a):
         ctx.timer_mark()
         tick.plan(pos_d.ptr, vel_d.ptr, xref_d.ptr)
         ctx.timer_mark()
+        chk = tick.check(t_check.ptr, pos_d.ptr)
+        tick.target(E.YAW_SMOOTH, t_target.ptr, pos_d.ptr, yaw_d.ptr, tgt.ptrs())
         rp.advance_device(pd["ts"], pos_d.ptr, vel_d.ptr)
         ctx.synchronize()
         walls.append(time.perf_counter() - t)
+        raised.append(int(chk.get()["replan_flag"].sum()))
+        done.append(int(tgt.get()["done"].sum()))
+        print(f"replan {r}: {raised[-1]} of {I} vehicles raised replan, {done[-1]} done", file=sys.stderr, flush=True)
         st = rp.stats()
         branches.append([int(st["fanout"]), int(st["single_first"]), int(st["single_current"])])
         num, inr = tick.gate.num.get(), tick.gate.in_range.get()
@@ -129,7 +142,7 @@ def detector_loop(a):
                              "replan": med(ms[1:, 3])},
         "device_ms": {"gate": ms[:, 0].tolist(), "intent_prob": ms[:, 1].tolist(), "predict_traj": ms[:, 2].tolist(),
                       "replan": ms[:, 3].tolist()},
-        "k_hist": k_hist, "truncated": truncated, "branches": branches,
+        "k_hist": k_hist, "truncated": truncated, "branches": branches, "replan_raised": raised, "done": done,
         "last_replan_rank0": {"qps": int(its.size), "mean_iter": float(its.mean()), "p50_iter": float(np.median(its)),
                               "max_iter": int(its.max()),
                               "status_counts": {str(int(k)): int(v) for k, v in zip(*np.unique(sts, return_counts=True))},
@@ -139,8 +152,9 @@ def detector_loop(a):
         "qp_solves_per_s_rank0": float(its.size / med(fan)), "valid_plans": int(valid.sum()),
         "ref_start_idx_mean": float(paths.last_idx().mean()), "gen_s": gen_s,
         "build_id": impc.lib.impc_build_id().decode()}), flush=True)
-    for d in (pos_d, vel_d, xref_d, world_d, wvel_d, wsize_d):
+    for d in (pos_d, vel_d, xref_d, world_d, wvel_d, wsize_d, t_target, t_check, yaw_d):
         d.free()
+    tgt.free()
     tick.close()
     tracks.close()
     paths.close()
