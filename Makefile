@@ -38,12 +38,13 @@ DETECTH := $(HARNDIR)/libdetect_harness.so
 EXECH   := $(HARNDIR)/libexec_harness.so
 MFMODEL := $(HARNDIR)/sweep_mfma_model
 STMODEL := $(HARNDIR)/sweep_store_model
+CLUSTH  := $(HARNDIR)/libcluster_harness.so
 
 .PHONY: all lib oracle harness prof variant clean
 all: lib oracle harness
 lib: $(LIB)
 oracle: $(ORACLE)
-harness: $(HARNESS) $(EMU) $(EMU64) $(SHIMT) $(REPLANX) $(DETECTH) $(EXECH) $(MFMODEL) $(STMODEL)
+harness: $(HARNESS) $(EMU) $(EMU64) $(SHIMT) $(REPLANX) $(DETECTH) $(EXECH) $(MFMODEL) $(STMODEL) $(CLUSTH)
 
 # (every source and header of the library: the build identity above is taken over the same list)
 $(LIBDIR)/impc_qp.o: $(CSRC)/impc_qp.hip $(SRCS)
@@ -55,7 +56,7 @@ prof: $(PROFLIB)
 $(LIBDIR)/impc_qp_prof.o: $(CSRC)/impc_qp.hip $(SRCS)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) $(call IDFLAGS,-prof) -DIMPC_SECTION_PROF -c $< -o $@
-$(PROFLIB): $(LIBDIR)/impc_qp_prof.o $(LIBDIR)/replan_run.o $(LIBDIR)/symbolic.o $(LIBDIR)/mpc_qp.o $(LIBDIR)/mpc_structure.o $(LIBDIR)/minsnap.o
+$(PROFLIB): $(LIBDIR)/impc_qp_prof.o $(LIBDIR)/replan_run.o $(LIBDIR)/cluster.o $(LIBDIR)/symbolic.o $(LIBDIR)/mpc_qp.o $(LIBDIR)/mpc_structure.o $(LIBDIR)/minsnap.o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $^ -o $@ $(LDLIBS)
 
 # the batched makePlanWithPred (include/impc_replan.h impc_replan_*): host orchestration + small
@@ -63,6 +64,12 @@ $(PROFLIB): $(LIBDIR)/impc_qp_prof.o $(LIBDIR)/replan_run.o $(LIBDIR)/symbolic.o
 $(LIBDIR)/replan_run.o: $(CSRC)/replan_run.hip $(CSRC)/lib_internal.hpp $(ROOT)/include/impc_replan.h \
 		$(ROOT)/include/impc_qp.h $(ROOT)/include/impc_mpc.h $(ROOT)/include/impc_fanout.h $(ROOT)/include/impc_select.h \
 		$(ROOT)/include/impc_comm.h $(ROOT)/include/impc_exec.h $(ROOT)/include/impc_predict.h $(CSRC)/plan_exec.hpp
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# the static-obstacle producer (include/impc_cluster.h): region scan, DBSCAN, 2-means tree, boxes
+$(LIBDIR)/cluster.o: $(CSRC)/cluster.hip $(CSRC)/cluster.hpp $(CSRC)/lib_internal.hpp $(ROOT)/include/impc_cluster.h \
+		$(ROOT)/include/impc_qp.h $(ROOT)/include/impc_predict.h $(ROOT)/include/impc_mpc.h $(ROOT)/include/impc_comm.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -82,7 +89,7 @@ $(LIBDIR)/mpc_structure.o: $(CSRC)/mpc_structure.cpp $(CSRC)/mpc_structure.hpp
 	@mkdir -p $(LIBDIR)
 	$(CXX) $(HOSTFLAGS) -c $< -o $@
 
-$(LIB): $(LIBDIR)/impc_qp.o $(LIBDIR)/replan_run.o $(LIBDIR)/symbolic.o $(LIBDIR)/mpc_qp.o $(LIBDIR)/mpc_structure.o $(LIBDIR)/minsnap.o
+$(LIB): $(LIBDIR)/impc_qp.o $(LIBDIR)/replan_run.o $(LIBDIR)/cluster.o $(LIBDIR)/symbolic.o $(LIBDIR)/mpc_qp.o $(LIBDIR)/mpc_structure.o $(LIBDIR)/minsnap.o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $^ -o $@ $(LDLIBS)
 
 $(ORACLE): $(ROOT)/oracle/osqp_oracle.c
@@ -131,6 +138,12 @@ $(EXECH): $(ROOT)/tests/native/exec_harness.cpp $(CSRC)/plan_exec.hpp $(ROOT)/in
 	@mkdir -p $(HARNDIR)
 	$(HIPCC) -x hip --offload-host-only -std=c++17 -O2 -fPIC -shared -ffp-contract=off $< -o $@
 
+# the serial form of the static-obstacle producer (csrc/cluster.hpp) compiled for the host
+$(CLUSTH): $(ROOT)/tests/native/cluster_harness.cpp $(CSRC)/cluster.hpp $(ROOT)/include/impc_cluster.h \
+		$(ROOT)/include/impc_predict.h
+	@mkdir -p $(HARNDIR)
+	$(HIPCC) -x hip --offload-host-only -std=c++17 -O2 -fPIC -shared -ffp-contract=off -Wall -Wno-unused-function $< -o $@ -lpthread
+
 # host model of the stage recursions on the FP64 matrix instruction against a plain loop (stand-alone,
 # host only; SAN="-fsanitize=address,undefined" for a checked build)
 $(MFMODEL): $(ROOT)/tests/native/sweep_mfma_model.cpp $(CSRC)/sweep_mfma_map.hpp
@@ -144,7 +157,7 @@ $(STMODEL): $(ROOT)/tests/native/sweep_store_model.cpp $(CSRC)/sweep_mfma_map.hp
 
 # kernel experiments (tools/ only): make variant V=name DEFS="-DX=1" -> lib/libimpc_qp_<name>.so,
 # selected at run time with IMPC_LIB_VARIANT=<name>
-variant: $(LIBDIR)/replan_run.o $(LIBDIR)/symbolic.o $(LIBDIR)/mpc_qp.o $(LIBDIR)/mpc_structure.o $(LIBDIR)/minsnap.o
+variant: $(LIBDIR)/replan_run.o $(LIBDIR)/cluster.o $(LIBDIR)/symbolic.o $(LIBDIR)/mpc_qp.o $(LIBDIR)/mpc_structure.o $(LIBDIR)/minsnap.o
 	$(HIPCC) $(HIPFLAGS) $(call IDFLAGS,-$(V)) $(DEFS) -c $(CSRC)/impc_qp.hip -o $(LIBDIR)/impc_qp_$(V).o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $(LIBDIR)/impc_qp_$(V).o $^ -o $(LIBDIR)/libimpc_qp_$(V).so $(LDLIBS)
 

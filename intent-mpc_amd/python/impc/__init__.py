@@ -272,6 +272,8 @@ EXPORTED = [
     "impc_batch_get_persistent", "impc_batch_get_occupancy",
     "impc_tracks_create", "impc_tracks_destroy", "impc_tracks_push_device", "impc_tracks_reset",
     "impc_detect_gather_device", "impc_detect_gather",  # bound in impc.perception
+    "impc_cluster_default_params", "impc_cluster_create", "impc_cluster_destroy", "impc_cluster_run_device",
+    "impc_cluster_run",  # bound in impc.clustering
 ]
 
 
