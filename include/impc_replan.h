@@ -207,6 +207,54 @@ int impc_replan_shape(impc_replan rp, int32_t obstacles, impc_batch *batch, int6
                       const double **l, const double **u);
 
 /* ======================================================================================
+ * Per-instance static-obstacle counts.  obclustering_->getStaticObstacles() returns each vehicle its
+ * own number of boxes (the device clustering's count [I], include/impc_cluster.h), and makePlan /
+ * makePlanWithPred pass exactly that many to solveTraj and getTrajectoryScore (:594, :615-620,
+ * :652).  A vehicle with fewer boxes cannot be padded -- updateObstacleParam's isDyamic quirk
+ * (:1151-1195) makes the QP's pattern depend on the pair (dynamic count, static count) -- so with
+ * counts bound every QP is grouped by that pair.
+ *
+ * impc_replan_bind_static_count: count_device [I] int32 in DEVICE memory, read on the stream by
+ * every later impc_replan_run (as num_pred is) and clamped to 0 .. S_st (S_st = num_static); the
+ * caller keeps it alive while bound.  Instance i then carries s_i = its clamped count: its boxes
+ * are rows 0 .. s_i - 1 of st_centroid / st_size / st_yaw [I][S_st].., rows >= s_i are never read.
+ *   first plan                 no static rows, shape K + 2, as without counts (:593-602);
+ *   every other single solve   s_i static rows after its dynamic ones, the quirk for (c_i, s_i);
+ *   every fan-out candidate    s_i static rows, the quirk for (K_i or K_i + 1, s_i);
+ *                              getTrajectoryScore scores the s_i boxes (:620, :816-848).
+ * NULL unbinds: every instance carries S_st again.  IMPC_INVALID_ARGUMENT: a null object or
+ * num_static = 0; IMPC_UNSUPPORTED: an object without solver shapes (as impc_replan_run).
+ *
+ * Shapes: ids 0 .. K + 2 keep their meaning (S_st static rows; K + 2: none).  The pair (k dynamic,
+ * s < S_st static rows), k in 0 .. K + 1, is shape id K + 3 + s (K + 2) + k, with shape k's
+ * capacity (I, 4 I, 2 I rows) and the same row order: single solves first, then candidates, each in
+ * ascending instance order.  view.shape[i] and the slots' shapes are these ids (a fan-out
+ * instance's candidates: the ids of (K_i, s_i) and (K_i + 1, s_i)).  The records keep their layout
+ * and their num_obs.
+ *
+ * The first non-NULL bind is a host call: it synchronises the context, creates the S_st (K + 2)
+ * further solver batches and builders, and re-uploads the shape table; when that fails (device
+ * memory, or a pattern the structured kernel does not take) whatever it created is freed, the
+ * object is exactly as before, and the error is returned.  Every later bind or unbind only stores
+ * the pointer, and impc_replan_run stays free of synchronisation and allocation.
+ *
+ * Device memory: every shape is sized for its worst case, so a bound object holds
+ *     (S_st + 1) x [ I + 4 I K + 2 I ] = (S_st + 1) (4 K + 3) I   QPs of solver storage (+ I first plans),
+ * S_st + 1 times that of the unbound object; the row tables grow alike (5 bytes per row).  (One
+ * capacity pooled over the static counts is not provided.)
+ *
+ * impc_replan_shape_static: impc_replan_shape of the pair (obstacles = k in 0 .. K + 1, statics = s
+ * in 0 .. S_st; s = S_st is shape k); s < S_st needs an object that has bound counts once.
+ * impc_replan_static_count_device: [I] (DEVICE, valid until destroy) the static rows each
+ * instance's QPs carried in the last run -- s_i, and 0 on a first plan.
+ * ====================================================================================== */
+int impc_replan_bind_static_count(impc_replan rp, const int32_t *count_device);
+int impc_replan_shape_static(impc_replan rp, int32_t obstacles, int32_t statics, impc_batch *batch, int64_t *count,
+                             const int32_t **row_inst, const int8_t **row_code, const double **Px, const double **q,
+                             const double **Ax, const double **l, const double **u);
+int impc_replan_static_count_device(impc_replan rp, const int32_t **count);
+
+/* ======================================================================================
  * What a replan decided, per planning instance, as one device-side record: the exchange of the
  * multi-GPU replan (every rank's records to every rank; the reference's caller needs each vehicle's
  * plan every 10 Hz tick, mpcNavigation.cpp:294-349).  A fixed 64-byte header, followed by

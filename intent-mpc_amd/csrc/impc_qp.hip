@@ -2678,19 +2678,32 @@ int comm_view(impc_comm c, impc_ctx *ctx, int *rank, int *world) {
 int build_rows(impc_mpc_builder bd, int64_t cap, const int64_t *dcount, const int32_t *row_inst, const int64_t *osrc,
                const double *pos, const double *vel, const double *xref, const double *lin, const double *pred_pos,
                const double *pred_size, const double *held_pos, const double *held_size, const double *st_centroid,
-               const double *st_size, const double *st_yaw, const BatchInputs &out, hipStream_t st) {
+               const double *st_size, const double *st_yaw, int32_t st_stride, const BatchInputs &out, hipStream_t st) {
     if (!bd || cap < 1) return fail(IMPC_INVALID_ARGUMENT, "build_rows: null builder or empty capacity");
     if (bd->S > 0 && (!st_centroid || !st_size || !st_yaw))
         return fail(IMPC_INVALID_ARGUMENT, "build_rows: static obstacles required by the builder");
+    if (bd->S > 0 && st_stride < bd->S)
+        return fail(IMPC_INVALID_ARGUMENT, "build_rows: the static arrays' stride is below the builder's count");
     impc_build::Args a{cap, bd->n, bd->m, bd->nnzP, bd->nnzA, bd->obs_off, bd->N, bd->W, bd->S, bd->Kd, bd->K, bd->L,
                        bd->p.dynamic_safety_dist, bd->p.static_safety_dist, bd->p.position_weight,
                        bd->p.velocity_weight, bd->d_tPx, bd->d_tAx, bd->d_tl, bd->d_tu, bd->d_slot, pos, vel, xref,
                        lin, st_centroid, st_size, st_yaw, pred_pos, pred_size, out.Px, out.q, out.Ax, out.l, out.u};
     a.dcount = dcount, a.row_inst = row_inst, a.osrc = osrc, a.hp = held_pos, a.hs = held_size;
+    a.Sst = st_stride;
     const int64_t groups = std::min<int64_t>(cap, (int64_t)bd->ctx->num_cu * 8);
     hipLaunchKernelGGL(impc_build::k_build, dim3((unsigned)groups), dim3(256), 0, st, a);
     HIP_OK(hipGetLastError());
     return IMPC_OK;
+}
+int select_best_counted(impc_ctx ctx, const impc_select_params *p, int64_t instances, const double *const *x_cand,
+                        const int8_t *valid, const int8_t *first_time, const double *prev_states,
+                        const int32_t *prev_count, const double *xref, const double *st_centroid,
+                        const double *st_size, const int32_t *st_count, const int32_t *dyn_count, const double *dyn_pos,
+                        const double *dyn_size, const double *prob, int32_t *best_cand, int32_t *best_pos,
+                        double *scores, double *weighted, void *stream) {
+    return impc_select::launch(ctx, p, instances, x_cand, valid, first_time, prev_states, prev_count, xref, st_centroid,
+                               st_size, st_count, dyn_count, dyn_pos, dyn_size, prob, best_cand, best_pos, scores,
+                               weighted, stream);
 }
 int batch_inputs_end(impc_batch b, bool warm_x) {
     if (!b) return fail(IMPC_INVALID_ARGUMENT, "null batch");

@@ -8,6 +8,7 @@
 #include "../../include/impc_comm.h"
 #include "../../include/impc_mpc.h"
 #include "../../include/impc_qp.h"
+#include "../../include/impc_select.h"
 
 namespace impc_lib {
 // solveTraj's success for one solved QP (mpcPlanner.cpp:475-478, :513-518): initSolver (osqp_setup)
@@ -50,10 +51,20 @@ double tick_s(impc_ctx ctx);
 // a communicator's context, rank and world size (comm.hpp)
 int comm_view(impc_comm c, impc_ctx *ctx, int *rank, int *world);
 // The device builder over replan rows (mpc_build.hpp Args: dcount / row_inst / osrc / held arrays;
-// static obstacles per instance, [*][builder's S][3] / [*][S], unread when the builder has none),
+// static obstacles per instance, [*][st_stride][3] / [*][st_stride] with st_stride >= the builder's S
+// boxes per instance, of which the builder reads the first S; unread when the builder has none),
 // writing the QP values into a batch's input arrays; asynchronous on `st`.
 int build_rows(impc_mpc_builder bd, int64_t cap, const int64_t *dcount, const int32_t *row_inst, const int64_t *osrc,
                const double *pos, const double *vel, const double *xref, const double *lin, const double *pred_pos,
                const double *pred_size, const double *held_pos, const double *held_size, const double *st_centroid,
-               const double *st_size, const double *st_yaw, const BatchInputs &out, hipStream_t st);
+               const double *st_size, const double *st_yaw, int32_t st_stride, const BatchInputs &out, hipStream_t st);
+// impc_select_best_device with a static-obstacle count per instance: st_count [I] in device memory
+// (0 .. p->num_static, clamped), instance i's getTrajectoryScore scoring its first st_count[i] boxes of
+// st_centroid / st_size [I][p->num_static][3]; NULL = p->num_static for every instance (the public call).
+int select_best_counted(impc_ctx ctx, const impc_select_params *p, int64_t instances, const double *const *x_cand,
+                        const int8_t *valid, const int8_t *first_time, const double *prev_states,
+                        const int32_t *prev_count, const double *xref, const double *st_centroid,
+                        const double *st_size, const int32_t *st_count, const int32_t *dyn_count, const double *dyn_pos,
+                        const double *dyn_size, const double *prob, int32_t *best_cand, int32_t *best_pos,
+                        double *scores, double *weighted, void *stream);
 }  // namespace impc_lib

@@ -34,6 +34,10 @@ struct Args {
     const int32_t *row_inst = nullptr;
     const int64_t *osrc = nullptr;
     const double *hp = nullptr, *hs = nullptr;
+    // Boxes per instance in stc / sts / sty (their per-instance stride): S for the plain layouts; a
+    // replan shape with S static rows below the object's S_st reads an instance's first S boxes of
+    // its S_st (impc_lib::build_rows' st_stride).
+    int32_t Sst = 0;
 };
 
 // ((std::pow(v, 2)) with glibc's correctly rounded pow is exactly the rounded product v * v)
@@ -91,10 +95,11 @@ __global__ __launch_bounds__(256) void k_build(Args a) {
                 yaw = 0.0;
             } else {
                 const int js = j - a.Kd;
-                const double *c = a.stc + (ib * a.S + js) * 3, *z = a.sts + (ib * a.S + js) * 3;
+                const int64_t sb = ib * a.Sst + js;
+                const double *c = a.stc + sb * 3, *z = a.sts + sb * 3;
                 ox = c[0], oy = c[1], oz = c[2];
                 sx = z[0] / 2 + a.ssafe, sy = z[1] / 2 + a.ssafe, sz = z[2] / 2 + a.ssafe;
-                yaw = a.sty[ib * a.S + js];
+                yaw = a.sty[sb];
             }
             double cx, cy, cz;  // linearisation point (:1042-1051)
             if (a.ls) {
@@ -190,6 +195,7 @@ extern "C" int impc_mpc_build_values_device(impc_mpc_builder b, int64_t nb, cons
                        b->p.dynamic_safety_dist, b->p.static_safety_dist, b->p.position_weight, b->p.velocity_weight,
                        b->d_tPx, b->d_tAx, b->d_tl, b->d_tu, b->d_slot, curr_pos, curr_vel, xref, lin_states,
                        st_centroid, st_size, st_yaw, dyn_pos, dyn_size, Px, q, Ax, l, u};
+    a.Sst = b->S;
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx->stream;
     const int64_t groups = std::min<int64_t>(nb, (int64_t)b->ctx->num_cu * 8);
     hipLaunchKernelGGL(impc_build::k_build, dim3((unsigned)groups), dim3(256), 0, st, a);

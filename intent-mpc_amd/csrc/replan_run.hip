@@ -8,9 +8,10 @@
 // Every instance may track a different number of obstacles (predPos.size(), :343-373).  Here every
 // instance of a batch goes through one call, and the call never waits for the device:
 //
-//   k_plan_rows   one workgroup: the branch of every instance and the rows of every QP shape
-//                 (shape k = the QPs with k obstacle rows per stage), by a scan over the instances;
-//                 the device clock at the start of the replan
+//   k_plan_rows   the branch of every instance and the rows of every QP shape (shape k = the QPs
+//                 with k dynamic-obstacle rows per stage; with per-instance static counts bound,
+//                 the pair (k, s_i)), by a scan over the instances, one workgroup per tile of
+//                 shapes; the device clock at the start of the replan
 //   k_pick        one thread per instance: findClosestObstacle + getIntentComb's candidate order
 //   k_prep        one wavefront per row: the warm start, the time limit and the obstacle sources
 //                 (which prediction / current obstacle each obstacle row linearises)
@@ -58,6 +59,7 @@
 namespace impc_rp {
 
 constexpr int kPlanLanes = 512;
+constexpr int kPlanTile = 14;  // shapes per workgroup of the row scan: (2 * 14 + 3) * 520 int32 = 63 KB of LDS
 constexpr int kMaxObstacles = 30;
 constexpr int FORWARD = 0, LEFT = 1, RIGHT = 2, STOP = 3;  // dynamicPredictor's intent enum
 
@@ -81,6 +83,35 @@ __host__ __device__ inline int shape_of(int64_t I, int K, int64_t f) {
 }
 // the dynamic-obstacle rows per stage of shape k's QPs
 __host__ __device__ inline int shape_dyn(int K, int k) { return k <= K + 1 ? k : 0; }
+
+// With per-instance static counts bound (impc_replan_bind_static_count) a shape is the pair (k
+// dynamic rows, s static rows).  Ids 0 .. K + 2 are the shapes above (s = S_st; K + 2: none); the
+// pair (k, s < S_st), k in 0 .. K + 1, has id K + 3 + s (K + 2) + k and shape k's capacity, its rows
+// after the I (4 K + 4) rows of ids 0 .. K + 2: block s of I (4 K + 3) rows laid out as ids 0 .. K + 1.
+__host__ __device__ inline int shape_id(int K, int nst, int k, int s) {
+    return s >= nst ? k : K + 3 + s * (K + 2) + k;
+}
+__host__ __device__ inline int64_t xshape_base(int64_t I, int K, int id) {
+    if (id <= K + 2) return shape_base(I, K, id);
+    const int e = id - (K + 3);
+    return I * (4 * (int64_t)K + 4) + (int64_t)(e / (K + 2)) * I * (4 * (int64_t)K + 3) + shape_base(I, K, e % (K + 2));
+}
+__host__ __device__ inline int64_t xshape_cap(int64_t I, int K, int id) {
+    return shape_cap(I, K, id <= K + 2 ? id : (id - (K + 3)) % (K + 2));
+}
+__host__ __device__ inline int xshape_of(int64_t I, int K, int64_t f) {
+    const int64_t r0 = I * (4 * (int64_t)K + 4), blk = I * (4 * (int64_t)K + 3);
+    if (f < r0) return shape_of(I, K, f);
+    const int64_t g = f - r0;
+    return K + 3 + (int)(g / blk) * (K + 2) + shape_of(I, K, g % blk);
+}
+__host__ __device__ inline int xshape_dyn(int K, int id) {
+    return id <= K + 2 ? shape_dyn(K, id) : (id - (K + 3)) % (K + 2);
+}
+// the static-obstacle rows per stage of shape id's QPs
+__host__ __device__ inline int xshape_stat(int K, int nst, int id) {
+    return id <= K + 1 ? nst : id == K + 2 ? 0 : (id - (K + 3)) / (K + 2);
+}
 
 // per-shape device pointers, fixed when the replan object is created
 struct ShapeDev {
@@ -106,45 +137,71 @@ struct Decide {
 
 struct PlanArgs {
     int64_t I;
-    int32_t K, S, first_shape;  // first_shape: the first plans' shape (K + 2 with static obstacles, else 0)
+    int32_t K, T, tile, nst, first_shape;  // T shapes in tiles of `tile`; first_shape: the first plans'
+                                           // shape (K + 2 with static obstacles, else 0)
     Decide decide;
+    const int32_t *scount;      // [I] bound static counts, or null: nst for every instance
     int8_t *branch;
-    int32_t *num_obs, *shp, *slot_row, *best;
+    int32_t *num_obs, *shp, *slot_row, *best, *scnt;
     int32_t *row_inst;
     int8_t *row_code;
-    int64_t *cnt;               // [S] single solves per shape, [S .. 2S) rows per shape, [2S .. 2S+3) branches
+    int64_t *cnt;               // [T] single solves per shape, [T .. 2T) rows per shape, [2T .. 2T+3) branches
     unsigned long long *clk;    // [0] the device clock at the start of the replan
 };
 
-// The shape of a single solve: a first plan's QP has no obstacle rows (static and dynamic obstacles
-// cleared, :593-602), any other has the current obstacles' c_i (0 with SINGLE_FIRST) and the statics.
-__device__ inline int single_shape(const PlanArgs &a, int64_t i, int br, int ci) {
-    return br == IMPC_REPLAN_SINGLE_CURRENT ? ci : a.decide.first_time[i] != 0 ? a.first_shape : 0;
+// The shapes of one instance: its single solve's (a first plan's QP has no obstacle rows -- static
+// and dynamic obstacles cleared, :593-602 --, any other has the current obstacles' c_i (0 with
+// SINGLE_FIRST) and the instance's s_i statics), or its candidates' two (K_i and K_i + 1 dynamic rows).
+struct InstShapes {
+    int br, ki, ci, si, id0, id1;  // id0: the single solve's / the single-intent candidates' shape
+    bool first;
+};
+__device__ inline InstShapes inst_shapes(const PlanArgs &a, int64_t i) {
+    InstShapes r;
+    a.decide(i, r.br, r.ki, r.ci);
+    r.si = a.scount ? min(max(a.scount[i], 0), a.nst) : a.nst;
+    r.first = a.decide.first_time[i] != 0;
+    if (r.br == IMPC_REPLAN_FANOUT) {
+        r.id0 = shape_id(a.K, a.nst, r.ki, r.si);
+        r.id1 = shape_id(a.K, a.nst, r.ki + 1, r.si);
+    } else {
+        r.id0 = r.br == IMPC_REPLAN_SINGLE_CURRENT ? shape_id(a.K, a.nst, r.ci, r.si)
+                : r.first                          ? a.first_shape
+                                                   : shape_id(a.K, a.nst, 0, r.si);
+        r.id1 = -1;
+    }
+    return r;
 }
 
-// One workgroup of kPlanLanes lanes, lane t owning a contiguous range of instances.  Counters
-// [R = 2S + 3][kPlanLanes] in LDS (rows 0..S-1: single solves of shape k, S..2S-1: candidate rows
-// of shape k, 2S..2S+2: instances per branch), an exclusive scan over the lanes (a wavefront scan
-// of 64 lanes, then the wavefront totals), and a second pass that writes each instance's rows in
-// ascending order: every shape holds its single solves first, then its candidates.
+// One workgroup of kPlanLanes lanes per tile of `tile` consecutive shape ids (one tile holds every
+// shape of an object without bound static counts up to K = 11, so the LDS is bounded whatever the
+// shape count: with counts bound the (K + 2)(S_st + 1) + 1 shapes spread over more workgroups, each
+// deciding every instance again and keeping only its own shapes' rows).  Lane t owns a contiguous
+// range of instances.  Counters [R = 2 tile + 3][kPlanLanes] in LDS (rows 0..tile-1: single solves
+// of the tile's shapes, tile..2 tile-1: their candidate rows, the last three: instances per branch),
+// an exclusive scan over the lanes (a wavefront scan of 64 lanes, then the wavefront totals), and a
+// second pass that writes each instance's rows in ascending order: every shape holds its single
+// solves first, then its candidates.  An instance's per-instance outputs are written by the
+// workgroup of its shape id0, slots 4 and 5 of a fan-out instance by that of id1.
 __global__ __launch_bounds__(kPlanLanes) void k_plan_rows(PlanArgs a) {
     extern __shared__ int32_t cl[];  // [R][kPlanLanes], then wave totals [R][kPlanLanes / 64]
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, NW = kPlanLanes / 64;
-    const int S = a.S, R = 2 * S + 3;
+    const int S = a.tile, R = 2 * S + 3, T = a.T;
+    const int s0 = (int)blockIdx.x * S, s1 = min(T, s0 + S);  // this workgroup's shape ids
     int32_t *wt = cl + R * kPlanLanes;
-    if (t == 0) a.clk[0] = wall_clock64();
+    if (t == 0 && blockIdx.x == 0) a.clk[0] = wall_clock64();
     const int64_t per = (a.I + kPlanLanes - 1) / kPlanLanes;
     const int64_t i0 = min(a.I, (int64_t)t * per), i1 = min(a.I, i0 + per);
+    const auto mine = [&](int id) { return id >= s0 && id < s1; };
     for (int r = 0; r < R; r++) cl[r * kPlanLanes + t] = 0;
     for (int64_t i = i0; i < i1; i++) {
-        int br, ki, ci;
-        a.decide(i, br, ki, ci);
-        cl[(2 * S + br) * kPlanLanes + t]++;
-        if (br == IMPC_REPLAN_FANOUT) {
-            cl[(S + ki) * kPlanLanes + t] += 4;
-            cl[(S + ki + 1) * kPlanLanes + t] += 2;
-        } else {
-            cl[single_shape(a, i, br, ci) * kPlanLanes + t]++;
+        const InstShapes d = inst_shapes(a, i);
+        cl[(2 * S + d.br) * kPlanLanes + t]++;
+        if (d.br == IMPC_REPLAN_FANOUT) {
+            if (mine(d.id0)) cl[(S + d.id0 - s0) * kPlanLanes + t] += 4;
+            if (mine(d.id1)) cl[(S + d.id1 - s0) * kPlanLanes + t] += 2;
+        } else if (mine(d.id0)) {
+            cl[(d.id0 - s0) * kPlanLanes + t]++;
         }
     }
     for (int r = 0; r < R; r++) {  // exclusive scan inside each wavefront
@@ -169,40 +226,42 @@ __global__ __launch_bounds__(kPlanLanes) void k_plan_rows(PlanArgs a) {
         return s;
     };
     for (int64_t i = i0; i < i1; i++) {
-        int br, ki, ci;
-        a.decide(i, br, ki, ci);
-        a.branch[i] = (int8_t)br;
-        a.best[i] = -1;
+        const InstShapes d = inst_shapes(a, i);
         int32_t *sr = a.slot_row + 6 * i;
-        for (int s = 0; s < 6; s++) sr[s] = -1;
-        if (br == IMPC_REPLAN_FANOUT) {
-            a.num_obs[i] = ki;
-            a.shp[i] = ki;
+        if (mine(d.id0)) {
+            a.branch[i] = (int8_t)d.br;
+            a.best[i] = -1;
+            a.shp[i] = d.id0;
+            a.scnt[i] = (d.br == IMPC_REPLAN_SINGLE_FIRST && d.first) ? 0 : d.si;
+            a.num_obs[i] = d.br == IMPC_REPLAN_FANOUT ? d.ki : d.br == IMPC_REPLAN_SINGLE_FIRST ? 0 : d.ci;
+        }
+        if (d.br == IMPC_REPLAN_FANOUT) {
             for (int s = 0; s < 6; s++) {
-                const int k = s < 4 ? ki : ki + 1;
-                const int64_t r = total(k) + cl[(S + k) * kPlanLanes + t]++;
-                const int64_t f = shape_base(a.I, a.K, k) + r;
+                const int id = s < 4 ? d.id0 : d.id1;
+                if (!mine(id)) continue;
+                const int64_t r = total(id - s0) + cl[(S + id - s0) * kPlanLanes + t]++;
+                const int64_t f = xshape_base(a.I, a.K, id) + r;
                 a.row_inst[f] = (int32_t)i;
                 a.row_code[f] = (int8_t)s;
                 sr[s] = (int32_t)r;
             }
-        } else {
-            const int k = single_shape(a, i, br, ci);
-            const int64_t r = cl[k * kPlanLanes + t]++;
-            const int64_t f = shape_base(a.I, a.K, k) + r;
+        } else if (mine(d.id0)) {
+            const int64_t r = cl[(d.id0 - s0) * kPlanLanes + t]++;
+            const int64_t f = xshape_base(a.I, a.K, d.id0) + r;
             a.row_inst[f] = (int32_t)i;
-            a.row_code[f] = (int8_t)(br == IMPC_REPLAN_SINGLE_FIRST ? IMPC_REPLAN_ROW_FIRST : IMPC_REPLAN_ROW_CURRENT);
-            a.num_obs[i] = br == IMPC_REPLAN_SINGLE_FIRST ? 0 : ci;
-            a.shp[i] = k;
+            a.row_code[f] =
+                (int8_t)(d.br == IMPC_REPLAN_SINGLE_FIRST ? IMPC_REPLAN_ROW_FIRST : IMPC_REPLAN_ROW_CURRENT);
             sr[0] = (int32_t)r;
+            for (int s = 1; s < 6; s++) sr[s] = -1;
         }
     }
     if (t == 0) {
-        for (int k = 0; k < S; k++) {
-            a.cnt[k] = total(k);
-            a.cnt[S + k] = total(k) + total(S + k);
+        for (int id = s0; id < s1; id++) {
+            a.cnt[id] = total(id - s0);
+            a.cnt[T + id] = total(id - s0) + total(S + id - s0);
         }
-        for (int b = 0; b < 3; b++) a.cnt[2 * S + b] = total(2 * S + b);
+        if (blockIdx.x == 0)
+            for (int b = 0; b < 3; b++) a.cnt[2 * T + b] = total(2 * S + b);
     }
 }
 
@@ -315,7 +374,7 @@ __device__ inline void cand_obstacle(int ob, int t, bool pair, int o, const doub
 
 struct PrepArgs {
     int64_t I, n, total;
-    int32_t K, L, S;
+    int32_t K, L, T;
     const int64_t *cnt;
     const ShapeDev *sh;
     const int32_t *row_inst, *ob, *slot_type;
@@ -330,9 +389,9 @@ struct PrepArgs {
 // sources of its obstacle rows for the builder.
 __global__ __launch_bounds__(64) void k_prep(PrepArgs a) {
     for (int64_t f = blockIdx.x; f < a.total; f += gridDim.x) {
-        const int k = shape_of(a.I, a.K, f);
-        const int64_t r = f - shape_base(a.I, a.K, k);
-        if (r >= a.cnt[a.S + k]) continue;
+        const int k = xshape_of(a.I, a.K, f);
+        const int64_t r = f - xshape_base(a.I, a.K, k);
+        if (r >= a.cnt[a.T + k]) continue;
         const ShapeDev sd = a.sh[k];
         const int64_t i = a.row_inst[f];
         const int code = a.row_code[f];
@@ -340,7 +399,7 @@ __global__ __launch_bounds__(64) void k_prep(PrepArgs a) {
         double *dst = sd.xws + r * a.n;
         for (int64_t e = threadIdx.x; e < a.n; e += blockDim.x) dst[e] = src[e];
         if (threadIdx.x == 0) sd.tlim[r] = code < 6 ? a.cand_limit : 0.0;
-        const int kd = shape_dyn(a.K, k);
+        const int kd = xshape_dyn(a.K, k);
         for (int o = threadIdx.x; o < kd; o += blockDim.x) {
             int64_t off;
             if (code == IMPC_REPLAN_ROW_CURRENT) {  // held over the horizon
@@ -357,23 +416,23 @@ __global__ __launch_bounds__(64) void k_prep(PrepArgs a) {
 
 // The issue cut-off (:612-613) after the assembly, on the device clock; the solve count of each
 // shape (its single solves always, its candidates when issued)
-__global__ void k_issue(int32_t S, int64_t *cnt, int64_t *solve, unsigned long long *clk, int32_t *issued_out,
+__global__ void k_issue(int32_t T, int64_t *cnt, int64_t *solve, unsigned long long *clk, int32_t *issued_out,
                         double elapsed_s, double tick, double cutoff) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const unsigned long long now = wall_clock64();
     clk[1] = now;
     const double elapsed = elapsed_s + (double)(now - clk[0]) * tick;
     const bool issued = !(cutoff > 0.0) || elapsed < cutoff;
-    for (int k = 0; k < S; k++) solve[k] = issued ? cnt[S + k] : cnt[k];
+    for (int k = 0; k < T; k++) solve[k] = issued ? cnt[T + k] : cnt[k];
     *issued_out = issued ? 1 : 0;
 }
 
 struct CandArgs {
     int64_t I, n;
-    int32_t K, L;
+    int32_t K, L, nst;
     const ShapeDev *sh;
     const int8_t *branch;
-    const int32_t *num_obs, *slot_row, *cslot, *slot_type, *ob;
+    const int32_t *num_obs, *scnt, *slot_row, *cslot, *slot_type, *ob;
     const int32_t *issued;
     const double *pred_pos, *pred_size, *prob;
     const double **x_cand;
@@ -394,9 +453,10 @@ __global__ void k_cand(CandArgs a) {
             continue;
         }
         const int s = a.cslot[e], k = s < 4 ? a.num_obs[i] : a.num_obs[i] + 1;
+        const int id = shape_id(a.K, a.nst, k, a.scnt[i]);
         const int64_t r = a.slot_row[6 * i + s];
-        a.valid[e] = (*a.issued && impc_lib::solve_traj_ok(a.sh[k].info[r])) ? 1 : 0;
-        a.x_cand[e] = a.sh[k].x + r * a.n;
+        a.valid[e] = (*a.issued && impc_lib::solve_traj_ok(a.sh[id].info[r])) ? 1 : 0;
+        a.x_cand[e] = a.sh[id].x + r * a.n;
         a.dyn_count[e] = k;
     }
 }
@@ -466,10 +526,10 @@ __global__ __launch_bounds__(64) void k_commit(CommitArgs a) {
 
 struct PackArgs {
     int64_t I, max_inst, inst_base;
-    int32_t N, P, rank;
+    int32_t N, P, rank, K, nst;
     const ShapeDev *sh;
     const int8_t *branch, *valid, *first_time;
-    const int32_t *prev_count, *best, *num_obs, *ob, *cslot, *slot_row, *shp;
+    const int32_t *prev_count, *best, *num_obs, *scnt, *ob, *cslot, *slot_row, *shp;
     const double *weighted, *plan_states;
     uint64_t *out;  // [max_inst][8 + 8 P] 64-bit words
 };
@@ -497,7 +557,7 @@ __global__ __launch_bounds__(64) void k_pack_records(PackArgs a) {
         if (br == IMPC_REPLAN_FANOUT) {
             if (b >= 0) {
                 const int s = a.cslot[6 * i + b];
-                k = s < 4 ? a.num_obs[i] : a.num_obs[i] + 1;
+                k = shape_id(a.K, a.nst, s < 4 ? a.num_obs[i] : a.num_obs[i] + 1, a.scnt[i]);
                 r = a.slot_row[6 * i + s];
                 score = a.weighted[6 * i + b];
             }
@@ -561,9 +621,19 @@ struct Arena {
     int get(size_t count, T **out) {
         return alloc(count * sizeof(T), (void **)out);
     }
-    void release() {
-        for (void *p : ptrs) (void)hipFree(p);
-        ptrs.clear();
+    void release() { release_from(0); }
+    // free everything allocated after the first `mark` allocations
+    void release_from(size_t mark) {
+        while (ptrs.size() > mark) {
+            (void)hipFree(ptrs.back());
+            ptrs.pop_back();
+        }
+    }
+    void drop(void *p) {
+        auto it = std::find(ptrs.begin(), ptrs.end(), p);
+        if (it == ptrs.end()) return;
+        (void)hipFree(p);
+        ptrs.erase(it);
     }
 };
 
@@ -587,6 +657,9 @@ struct impc_replan_s {
     impc_replan_config cfg{};
     int64_t I = 0, n = 0, rows = 0;
     int32_t N = 0, K = 0, L = 0, S = 0;
+    int32_t T = 0;                      // shapes in all: S, or S + S_st (K + 2) once static counts were bound
+    const int32_t *scount = nullptr;    // the bound per-instance static counts (DEVICE, the caller's)
+    int32_t *scnt = nullptr;            // [I] static rows of each instance's QPs in the last run
     Arena mem;
     // planner state
     double *plan_x = nullptr, *plan_states = nullptr;
@@ -609,7 +682,8 @@ struct impc_replan_s {
     double *dyn_pos = nullptr, *dyn_size = nullptr, *scores = nullptr, *weighted = nullptr;
     int8_t *cvalid = nullptr;
     int32_t nst = 0;        // static obstacles per instance (cfg.num_static)
-    std::vector<Shape> sh;  // S = K + 2 shapes by dynamic-obstacle count, + the first plans' with statics
+    std::vector<Shape> sh;  // by shape id: S = K + 2 shapes by dynamic-obstacle count, + the first plans' with
+                            // statics, + the (k, s < S_st) pairs once static counts were bound
     std::vector<impc_batch> group;
     impc_replan_stats stats{};
     bool ran = false;
@@ -620,6 +694,10 @@ struct impc_replan_s {
 namespace {
 
 int fail(int code, const char *msg) { return impc_lib::set_error(code, msg); }
+
+const char *const kNoShapes = "replan: the horizon / obstacle count is beyond the structured kernel "
+                              "(the object only holds plan state)";
+const char *const kNoStatic = "replan: per-instance static counts need num_static > 0";
 
 // *no_kernel: the pattern is not one the structured kernel takes (the only kernel of the grouped solve)
 int make_shape(impc_replan rp, Shape &s, int32_t k, int32_t nst, int64_t cap, bool *no_kernel) {
@@ -686,6 +764,7 @@ int impc_replan_create(impc_ctx ctx, const impc_replan_config *cfg, impc_replan 
     rp->cfg = *cfg;
     rp->I = I, rp->N = N, rp->K = K, rp->L = L, rp->nst = cfg->num_static;
     rp->S = K + 2 + (rp->nst > 0 ? 1 : 0);
+    rp->T = rp->S;
     rp->n = 13 * (int64_t)N - 5;
     rp->rows = shape_base(I, K, rp->S - 1) + shape_cap(I, K, rp->S - 1);
     const int64_t n = rp->n, S = rp->S;
@@ -713,6 +792,7 @@ int impc_replan_create(impc_ctx ctx, const impc_replan_config *cfg, impc_replan 
     RP_CK(a.get((size_t)rp->rows, &rp->row_code));
     RP_CK(a.get((size_t)I, &rp->num_obs));
     RP_CK(a.get((size_t)I, &rp->shp));
+    RP_CK(a.get((size_t)I, &rp->scnt));
     RP_CK(a.get((size_t)(6 * I), &rp->slot_row));
     RP_CK(a.get((size_t)(6 * I), &rp->slot_type));
     RP_CK(a.get((size_t)I, &rp->best));
@@ -736,6 +816,7 @@ int impc_replan_create(impc_ctx ctx, const impc_replan_config *cfg, impc_replan 
     hipStream_t st = impc_lib::stream(ctx);
     if (hipMemsetAsync(rp->zeros8, 0, (size_t)I, st) != hipSuccess ||
         hipMemsetAsync(rp->valid, 0, (size_t)I, st) != hipSuccess ||
+        hipMemsetAsync(rp->scnt, 0, sizeof(int32_t) * (size_t)I, st) != hipSuccess ||
         hipMemsetAsync(rp->plan_ref, 0, sizeof(double) * (size_t)(I * N * 3), st) != hipSuccess ||
         hipMemsetAsync(rp->cnt, 0, sizeof(int64_t) * (size_t)(2 * S + 3), st) != hipSuccess ||
         hipMemsetAsync(rp->solve, 0, sizeof(int64_t) * (size_t)S, st) != hipSuccess) {
@@ -769,15 +850,6 @@ int impc_replan_create(impc_ctx ctx, const impc_replan_config *cfg, impc_replan 
     }
     if (!rp->sh.empty())
         RP_CK(impc_copy_to_device(ctx, rp->d_sh, hdev.data(), (int64_t)(sizeof(ShapeDev) * hdev.size())));
-    {  // the row scan's counters: (2 S + 3) x (lanes + wave totals) int32 of LDS
-        const size_t lds = sizeof(int32_t) * (size_t)(2 * S + 3) * (kPlanLanes + kPlanLanes / 64);
-        if (lds > 64 * 1024 &&
-            hipFuncSetAttribute((const void *)k_plan_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-                hipSuccess) {
-            cleanup();
-            return fail(IMPC_DEVICE_ERROR, "replan: LDS of the row scan");
-        }
-    }
 #undef RP_CK
     rc = impc_replan_set_state(rp.get(), nullptr, nullptr);
     if (rc) {
@@ -847,33 +919,36 @@ int impc_replan_run(impc_replan rp, const impc_replan_inputs *in) {
     if (in->cur_count && !in->cur_size) return fail(IMPC_INVALID_ARGUMENT, "replan: cur_count needs cur_size");
     if (rp->nst > 0 && (!in->st_centroid || !in->st_size || !in->st_yaw))
         return fail(IMPC_INVALID_ARGUMENT, "replan: num_static > 0 needs st_centroid, st_size, st_yaw");
-    if (rp->sh.empty())
-        return fail(IMPC_UNSUPPORTED, "replan: the horizon / obstacle count is beyond the structured kernel "
-                                      "(the object only holds plan state)");
+    if (rp->sh.empty()) return fail(IMPC_UNSUPPORTED, kNoShapes);
     impc_ctx ctx = rp->ctx;
     RP_HIP(hipSetDevice(impc_lib::device(ctx)));
     hipStream_t st = impc_lib::stream(ctx);
     RP_TRY(impc_lib::order_after_all(ctx));
     const int64_t I = rp->I, n = rp->n;
-    const int32_t N = rp->N, K = rp->K, L = rp->L, S = rp->S;
+    const int32_t N = rp->N, K = rp->K, L = rp->L;
 
     // ---- the branch and the rows of every instance (:593-606)
+    const int32_t T = rp->T, tile = std::min<int32_t>(T, kPlanTile);
     PlanArgs pa{I,
                 K,
-                S,
+                T,
+                tile,
+                rp->nst,
                 rp->nst > 0 ? K + 2 : 0,
                 Decide{rp->first_time, in->has_pred, in->num_pred, in->cur_count, K, in->cur_size ? 1 : 0},
+                rp->scount,
                 rp->branch,
                 rp->num_obs,
                 rp->shp,
                 rp->slot_row,
                 rp->best,
+                rp->scnt,
                 rp->row_inst,
                 rp->row_code,
                 rp->cnt,
                 rp->clk};
-    const size_t lds = sizeof(int32_t) * (size_t)(2 * S + 3) * (kPlanLanes + kPlanLanes / 64);
-    hipLaunchKernelGGL(k_plan_rows, dim3(1), dim3(kPlanLanes), lds, st, pa);
+    const size_t lds = sizeof(int32_t) * (size_t)(2 * tile + 3) * (kPlanLanes + kPlanLanes / 64);
+    hipLaunchKernelGGL(k_plan_rows, dim3((unsigned)((T + tile - 1) / tile)), dim3(kPlanLanes), lds, st, pa);
     RP_HIP(hipGetLastError());
     // ---- the fan-out's closest obstacle and candidate order
     PickArgs pk{I, K, N, rp->branch, rp->num_obs, in->pos, rp->plan_states, in->dyn_cur, in->prob, rp->prev_count,
@@ -883,28 +958,28 @@ int impc_replan_run(impc_replan rp, const impc_replan_inputs *in) {
     // ---- warm starts, time limits, obstacle sources; the assembly of every shape in place
     // (timeLimit = max(solverTimeLimit_ - t, solverTimeLimit_) = solverTimeLimit_ for t >= 0, :614)
     const double tl = in->solver_time_limit > 0.0 ? in->solver_time_limit : rp->cfg.settings.time_limit;
-    PrepArgs pp{I, n, rp->rows, K, L, S, rp->cnt, rp->d_sh, rp->row_inst, rp->ob, rp->slot_type, rp->row_code,
+    PrepArgs pp{I, n, rp->rows, K, L, T, rp->cnt, rp->d_sh, rp->row_inst, rp->ob, rp->slot_type, rp->row_code,
                 rp->first_time, rp->plan_x, in->prob, tl};
     hipLaunchKernelGGL(k_prep, dim3(grid_for(rp, rp->rows, 1)), dim3(64), 0, st, pp);
     RP_HIP(hipGetLastError());
-    for (int32_t k = 0; k < S; k++) {
+    for (int32_t k = 0; k < T; k++) {
         Shape &s = rp->sh[(size_t)k];
         impc_lib::BatchInputs bi{};
         RP_TRY(impc_lib::batch_inputs_begin(s.batch, &bi));
-        const bool stat = s.nst > 0;
-        RP_TRY(impc_lib::build_rows(s.bld, s.cap, rp->cnt + S + k, rp->row_inst + shape_base(I, K, k), s.dev.osrc,
+        const bool stat = s.nst > 0;  // its first s.nst of the instance's S_st boxes
+        RP_TRY(impc_lib::build_rows(s.bld, s.cap, rp->cnt + T + k, rp->row_inst + xshape_base(I, K, k), s.dev.osrc,
                                     in->pos, in->vel, in->xref, rp->plan_states, in->pred_pos, in->pred_size,
                                     in->dyn_cur, in->cur_size, stat ? in->st_centroid : nullptr,
-                                    stat ? in->st_size : nullptr, stat ? in->st_yaw : nullptr, bi, st));
+                                    stat ? in->st_size : nullptr, stat ? in->st_yaw : nullptr, rp->nst, bi, st));
         RP_TRY(impc_lib::batch_inputs_end(s.batch, true));
     }
     // ---- the issue cut-off on the device clock; ONE grouped solve over every shape
-    hipLaunchKernelGGL(k_issue, dim3(1), dim3(64), 0, st, S, rp->cnt, rp->solve, rp->clk, rp->issued, in->elapsed_s,
+    hipLaunchKernelGGL(k_issue, dim3(1), dim3(64), 0, st, T, rp->cnt, rp->solve, rp->clk, rp->issued, in->elapsed_s,
                        impc_lib::tick_s(ctx), rp->cfg.issue_cutoff_s);
     RP_HIP(hipGetLastError());
     RP_TRY(impc_batch_solve_group(rp->group.data(), (int)rp->group.size(), nullptr));
     // ---- candidate validity, selection, commit
-    CandArgs ca{I, n, K, L, rp->d_sh, rp->branch, rp->num_obs, rp->slot_row, rp->cslot, rp->slot_type, rp->ob,
+    CandArgs ca{I, n, K, L, rp->nst, rp->d_sh, rp->branch, rp->num_obs, rp->scnt, rp->slot_row, rp->cslot, rp->slot_type, rp->ob,
                 rp->issued, in->pred_pos, in->pred_size, in->prob, rp->x_cand, rp->dyn_count, rp->cvalid, rp->dyn_pos,
                 rp->dyn_size};
     hipLaunchKernelGGL(k_cand, dim3(grid_for(rp, 6 * I)), dim3(256), 0, st, ca);
@@ -915,10 +990,12 @@ int impc_replan_run(impc_replan rp, const impc_replan_inputs *in) {
     sp.num_static = rp->nst, sp.prev_len = N;  // getTrajectoryScore's staticObstacles (:620)
     sp.dynamic_safety_dist = rp->cfg.mpc.dynamic_safety_dist;
     sp.static_safety_dist = rp->cfg.mpc.static_safety_dist;
-    RP_TRY(impc_select_best_device(ctx, &sp, I, rp->x_cand, rp->cvalid, rp->zeros8, rp->plan_states, rp->prev_count,
-                                   in->xref, rp->nst ? in->st_centroid : nullptr, rp->nst ? in->st_size : nullptr,
-                                   rp->dyn_count, rp->dyn_pos, rp->dyn_size, rp->cprob,
-                                   rp->best, rp->best_pos, rp->scores, rp->weighted, nullptr));
+    // (a fan-out instance is never on a first plan: scnt is its s_i, S_st without bound counts)
+    RP_TRY(impc_lib::select_best_counted(ctx, &sp, I, rp->x_cand, rp->cvalid, rp->zeros8, rp->plan_states,
+                                         rp->prev_count, in->xref, rp->nst ? in->st_centroid : nullptr,
+                                         rp->nst ? in->st_size : nullptr, rp->nst ? rp->scnt : nullptr, rp->dyn_count,
+                                         rp->dyn_pos, rp->dyn_size, rp->cprob, rp->best, rp->best_pos, rp->scores,
+                                         rp->weighted, nullptr));
     CommitArgs cm{I, n, N, rp->d_sh, rp->branch, rp->shp, rp->slot_row, rp->best, rp->x_cand, rp->plan_x,
                   rp->plan_states, rp->prev_count, rp->first_time, rp->valid};
     hipLaunchKernelGGL(k_commit, dim3(grid_for(rp, I, 1)), dim3(64), 0, st, cm);
@@ -939,7 +1016,7 @@ int impc_replan_get_stats(impc_replan rp, impc_replan_stats *out) {
     std::memset(out, 0, sizeof(*out));
     if (!rp->ran) return IMPC_OK;
     RP_TRY(impc_ctx_synchronize(rp->ctx));
-    const int32_t S = rp->S;
+    const int32_t S = rp->T;
     std::vector<int64_t> c((size_t)(2 * S + 3));
     unsigned long long ck[2];
     int32_t iss = 0;
@@ -966,21 +1043,20 @@ int impc_replan_view_device(impc_replan rp, impc_replan_view *out) {
     return IMPC_OK;
 }
 
-int impc_replan_shape(impc_replan rp, int32_t obstacles, impc_batch *batch, int64_t *count, const int32_t **row_inst,
-                      const int8_t **row_code, const double **Px, const double **q, const double **Ax,
-                      const double **l, const double **u) {
-    if (!rp || obstacles < 0 || obstacles >= rp->S)
-        return fail(IMPC_INVALID_ARGUMENT, "replan: shape must be in 0 .. num_obstacles + 1 (+ 2 with num_static)");
-    if (rp->sh.empty()) return fail(IMPC_UNSUPPORTED, "replan: no solver shapes (the object only holds plan state)");
-    const Shape &s = rp->sh[(size_t)obstacles];
+namespace {
+
+int shape_view(impc_replan rp, int32_t id, impc_batch *batch, int64_t *count, const int32_t **row_inst,
+               const int8_t **row_code, const double **Px, const double **q, const double **Ax, const double **l,
+               const double **u) {
+    const Shape &s = rp->sh[(size_t)id];
     int64_t c = 0;
     if (rp->ran) {
         RP_TRY(impc_ctx_synchronize(rp->ctx));
-        RP_TRY(impc_copy_to_host(rp->ctx, &c, rp->solve + obstacles, (int64_t)sizeof(c)));
+        RP_TRY(impc_copy_to_host(rp->ctx, &c, rp->solve + id, (int64_t)sizeof(c)));
     }
     if (batch) *batch = s.batch;
     if (count) *count = c;
-    const int64_t base = shape_base(rp->I, rp->K, obstacles);
+    const int64_t base = xshape_base(rp->I, rp->K, id);
     if (row_inst) *row_inst = rp->row_inst + base;
     if (row_code) *row_code = rp->row_code + base;
     impc_lib::BatchInputs bi{};
@@ -991,6 +1067,122 @@ int impc_replan_shape(impc_replan rp, int32_t obstacles, impc_batch *batch, int6
     if (l) *l = bi.l;
     if (u) *u = bi.u;
     return IMPC_OK;
+}
+
+// The shapes (k, s < S_st) of an object whose static counts are bound for the first time: their
+// solver batches and builders, and the row / count / shape tables at their full size (the last
+// run's contents carried over).  On any failure everything created here is freed and the object
+// is left as it was.
+int extend_shapes(impc_replan rp) {
+    impc_ctx ctx = rp->ctx;
+    RP_HIP(hipSetDevice(impc_lib::device(ctx)));
+    RP_TRY(impc_ctx_synchronize(ctx));
+    const int64_t I = rp->I;
+    const int32_t K = rp->K, S = rp->S, nst = rp->nst, T2 = S + nst * (K + 2);
+    const int64_t rows2 = xshape_base(I, K, T2 - 1) + xshape_cap(I, K, T2 - 1);
+    Arena &a = rp->mem;
+    const size_t mark = a.ptrs.size();
+    std::vector<Shape> ext((size_t)(T2 - S));
+    int32_t *row_inst = nullptr;
+    int8_t *row_code = nullptr;
+    int64_t *cnt = nullptr, *solve = nullptr;
+    ShapeDev *d_sh = nullptr;
+    int rc = IMPC_OK;
+    auto undo = [&]() {
+        for (Shape &s : ext) free_shape(s);
+        a.release_from(mark);
+    };
+#define RP_CK(expr)      \
+    if ((rc = (expr))) { \
+        undo();          \
+        return rc;       \
+    }
+    for (int32_t id = S; id < T2; id++) {
+        bool no_kernel = false;
+        RP_CK(make_shape(rp, ext[(size_t)(id - S)], xshape_dyn(K, id), xshape_stat(K, nst, id), xshape_cap(I, K, id),
+                         &no_kernel));
+    }
+    RP_CK(a.get((size_t)rows2, &row_inst));
+    RP_CK(a.get((size_t)rows2, &row_code));
+    RP_CK(a.get((size_t)(2 * T2 + 3), &cnt));
+    RP_CK(a.get((size_t)T2, &solve));
+    RP_CK(a.get((size_t)T2, &d_sh));
+    // the last run's tables in the new layout (ids 0 .. S - 1 keep their rows and counts)
+    std::vector<int64_t> c0((size_t)(2 * S + 3)), s0((size_t)S), c2((size_t)(2 * T2 + 3), 0), s2((size_t)T2, 0);
+    RP_CK(impc_copy_to_host(ctx, c0.data(), rp->cnt, (int64_t)(sizeof(int64_t) * c0.size())));
+    RP_CK(impc_copy_to_host(ctx, s0.data(), rp->solve, (int64_t)(sizeof(int64_t) * s0.size())));
+    for (int32_t k = 0; k < S; k++) {
+        c2[(size_t)k] = c0[(size_t)k];
+        c2[(size_t)(T2 + k)] = c0[(size_t)(S + k)];
+        s2[(size_t)k] = s0[(size_t)k];
+    }
+    for (int b = 0; b < 3; b++) c2[(size_t)(2 * T2 + b)] = c0[(size_t)(2 * S + b)];
+    RP_CK(impc_copy_to_device(ctx, cnt, c2.data(), (int64_t)(sizeof(int64_t) * c2.size())));
+    RP_CK(impc_copy_to_device(ctx, solve, s2.data(), (int64_t)(sizeof(int64_t) * s2.size())));
+    std::vector<ShapeDev> hdev((size_t)T2);
+    for (int32_t id = 0; id < T2; id++) hdev[(size_t)id] = id < S ? rp->sh[(size_t)id].dev : ext[(size_t)(id - S)].dev;
+    RP_CK(impc_copy_to_device(ctx, d_sh, hdev.data(), (int64_t)(sizeof(ShapeDev) * hdev.size())));
+    if (hipMemset(row_inst, 0, sizeof(int32_t) * (size_t)rows2) != hipSuccess ||
+        hipMemset(row_code, 0, (size_t)rows2) != hipSuccess ||
+        hipMemcpy(row_inst, rp->row_inst, sizeof(int32_t) * (size_t)rp->rows, hipMemcpyDeviceToDevice) != hipSuccess ||
+        hipMemcpy(row_code, rp->row_code, (size_t)rp->rows, hipMemcpyDeviceToDevice) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
+        undo();
+        return fail(IMPC_DEVICE_ERROR, "replan: copying the row tables");
+    }
+    for (int32_t id = S; id < T2; id++) {
+        RP_CK(impc_lib::batch_set_active_device(ext[(size_t)(id - S)].batch, solve + id));
+    }
+#undef RP_CK
+    // nothing below fails: the existing batches take the device count of the new table as they took the old
+    for (int32_t k = 0; k < S; k++) (void)impc_lib::batch_set_active_device(rp->sh[(size_t)k].batch, solve + k);
+    a.drop(rp->row_inst), a.drop(rp->row_code), a.drop(rp->cnt), a.drop(rp->solve), a.drop(rp->d_sh);
+    rp->row_inst = row_inst, rp->row_code = row_code, rp->cnt = cnt, rp->solve = solve, rp->d_sh = d_sh;
+    for (Shape &s : ext) {
+        rp->sh.push_back(s);
+        rp->group.push_back(s.batch);
+    }
+    rp->T = T2;
+    rp->rows = rows2;
+    return IMPC_OK;
+}
+
+}  // namespace
+
+int impc_replan_bind_static_count(impc_replan rp, const int32_t *count_device) {
+    if (!rp) return fail(IMPC_INVALID_ARGUMENT, "null replan");
+    if (rp->nst <= 0) return fail(IMPC_INVALID_ARGUMENT, kNoStatic);
+    if (rp->sh.empty()) return fail(IMPC_UNSUPPORTED, kNoShapes);
+    if (count_device && rp->T == rp->S) RP_TRY(extend_shapes(rp));
+    rp->scount = count_device;
+    return IMPC_OK;
+}
+
+int impc_replan_static_count_device(impc_replan rp, const int32_t **count) {
+    if (!rp || !count) return fail(IMPC_INVALID_ARGUMENT, "replan: null object or output");
+    *count = rp->scnt;
+    return IMPC_OK;
+}
+
+int impc_replan_shape(impc_replan rp, int32_t obstacles, impc_batch *batch, int64_t *count, const int32_t **row_inst,
+                      const int8_t **row_code, const double **Px, const double **q, const double **Ax,
+                      const double **l, const double **u) {
+    if (!rp || obstacles < 0 || obstacles >= rp->S)
+        return fail(IMPC_INVALID_ARGUMENT, "replan: shape must be in 0 .. num_obstacles + 1 (+ 2 with num_static)");
+    if (rp->sh.empty()) return fail(IMPC_UNSUPPORTED, "replan: no solver shapes (the object only holds plan state)");
+    return shape_view(rp, obstacles, batch, count, row_inst, row_code, Px, q, Ax, l, u);
+}
+
+int impc_replan_shape_static(impc_replan rp, int32_t obstacles, int32_t statics, impc_batch *batch, int64_t *count,
+                             const int32_t **row_inst, const int8_t **row_code, const double **Px, const double **q,
+                             const double **Ax, const double **l, const double **u) {
+    if (!rp || obstacles < 0 || obstacles > rp->K + 1 || statics < 0 || statics > rp->nst)
+        return fail(IMPC_INVALID_ARGUMENT, "replan: shape (k, s) must be in 0 .. num_obstacles + 1, 0 .. num_static");
+    if (rp->sh.empty()) return fail(IMPC_UNSUPPORTED, "replan: no solver shapes (the object only holds plan state)");
+    if (statics < rp->nst && rp->T == rp->S)
+        return fail(IMPC_INVALID_ARGUMENT, "replan: shapes below num_static exist once static counts were bound");
+    return shape_view(rp, shape_id(rp->K, rp->nst, obstacles, statics), batch, count, row_inst, row_code, Px, q, Ax, l,
+                      u);
 }
 
 namespace {
@@ -1012,8 +1204,9 @@ int check_pack(impc_replan rp, int64_t inst_base, int32_t plan_steps, int64_t ma
 int pack_records(impc_replan rp, int32_t rank, int64_t inst_base, int32_t plan_steps, int64_t max_inst, void *out) {
     RP_HIP(hipSetDevice(impc_lib::device(rp->ctx)));
     RP_TRY(impc_lib::order_after_all(rp->ctx));
-    PackArgs pk{rp->I, max_inst, inst_base, rp->N, plan_steps, rank, rp->d_sh, rp->branch, rp->valid, rp->first_time,
-                rp->prev_count, rp->best, rp->num_obs, rp->ob, rp->cslot, rp->slot_row, rp->shp, rp->weighted,
+    PackArgs pk{rp->I, max_inst, inst_base, rp->N, plan_steps, rank, rp->K, rp->nst, rp->d_sh, rp->branch, rp->valid,
+                rp->first_time, rp->prev_count, rp->best, rp->num_obs, rp->scnt, rp->ob, rp->cslot, rp->slot_row, rp->shp,
+                rp->weighted,
                 rp->plan_states, (uint64_t *)out};
     hipLaunchKernelGGL(k_pack_records, dim3(grid_for(rp, max_inst, 1)), dim3(64), 0, impc_lib::stream(rp->ctx), pk);
     RP_HIP(hipGetLastError());

@@ -24,6 +24,8 @@ struct Args {
     const double *dyn_pos, *dyn_size, *prob;
     int32_t *best_cand, *best_pos;
     double *scores, *weighted;
+    // static obstacles scored per instance (the first st_count[inst] of its S boxes); null: all S
+    const int32_t *st_count = nullptr;
 };
 
 __device__ inline double norm3(double a, double b, double c) { return sqrt(a * a + b * b + c * c); }
@@ -64,6 +66,7 @@ __global__ __launch_bounds__(64) void k_cand_scores(Args a) {
     const double *ds = a.dyn_size + ic * (int64_t)a.KMAX * a.L * 3;
     const double *sp = a.st_centroid + inst * (int64_t)a.S * 3;
     const double *ss = a.st_size + inst * (int64_t)a.S * 3;
+    const int Si = a.st_count ? min(max(a.st_count[inst], 0), a.S) : a.S;
     double saf = 0.0;
     for (int i = 0; i < a.N; i++) {
         double dist = 0.0, totw = 0.0;
@@ -76,7 +79,7 @@ __global__ __launch_bounds__(64) void k_cand_scores(Args a) {
             dist += d * w;
             totw += w;
         }
-        for (int j = 0; j < a.S; j++) {
+        for (int j = 0; j < Si; j++) {
             const double maxs = sqrt((ss[3 * j] / 2) * (ss[3 * j] / 2) + (ss[3 * j + 1] / 2) * (ss[3 * j + 1] / 2));
             const double d = norm3(px - sp[3 * j], py - sp[3 * j + 1], 0.0);
             const double w = 1 - tanh(catanh / (a.static_safety + maxs) * d);
@@ -137,15 +140,12 @@ __global__ __launch_bounds__(64) void k_select(Args a) {
     a.best_pos[inst] = bestpos;
 }
 
-}  // namespace impc_select
-
-extern "C" int impc_select_best_device(impc_ctx ctx, const impc_select_params *p, int64_t instances,
-                                       const double *const *x_cand, const int8_t *valid, const int8_t *first_time,
-                                       const double *prev_states, const int32_t *prev_count, const double *xref,
-                                       const double *st_centroid, const double *st_size, const int32_t *dyn_count,
-                                       const double *dyn_pos, const double *dyn_size, const double *prob,
-                                       int32_t *best_cand, int32_t *best_pos, double *scores, double *weighted,
-                                       void *stream) {
+// the two kernels on `stream` (null: the context stream); st_count as Args::st_count
+int launch(impc_ctx ctx, const impc_select_params *p, int64_t instances, const double *const *x_cand,
+           const int8_t *valid, const int8_t *first_time, const double *prev_states, const int32_t *prev_count,
+           const double *xref, const double *st_centroid, const double *st_size, const int32_t *st_count,
+           const int32_t *dyn_count, const double *dyn_pos, const double *dyn_size, const double *prob,
+           int32_t *best_cand, int32_t *best_pos, double *scores, double *weighted, void *stream) {
     if (!ctx || !p) return fail(IMPC_INVALID_ARGUMENT, "null argument");
     if (instances < 0 || p->horizon < 1 || p->num_candidates < 1 || p->num_candidates > 6 || p->max_dynamic < 0 ||
         p->pred_len < p->horizon || p->num_static < 0 || p->prev_len < 0)
@@ -156,6 +156,7 @@ extern "C" int impc_select_best_device(impc_ctx ctx, const impc_select_params *p
                         p->prev_len, p->dynamic_safety_dist, p->static_safety_dist, x_cand, valid, first_time,
                         prev_states, prev_count, xref, st_centroid, st_size, dyn_count, dyn_pos, dyn_size, prob,
                         best_cand, best_pos, scores, weighted};
+    a.st_count = st_count;
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     const int64_t ic = instances * p->num_candidates;
     hipLaunchKernelGGL(impc_select::k_cand_scores, dim3((unsigned)((ic + 63) / 64)), dim3(64), 0, st, a);
@@ -163,6 +164,20 @@ extern "C" int impc_select_best_device(impc_ctx ctx, const impc_select_params *p
     hipLaunchKernelGGL(impc_select::k_select, dim3((unsigned)((instances + 63) / 64)), dim3(64), 0, st, a);
     HIP_OK(hipGetLastError());
     return IMPC_OK;
+}
+
+}  // namespace impc_select
+
+extern "C" int impc_select_best_device(impc_ctx ctx, const impc_select_params *p, int64_t instances,
+                                       const double *const *x_cand, const int8_t *valid, const int8_t *first_time,
+                                       const double *prev_states, const int32_t *prev_count, const double *xref,
+                                       const double *st_centroid, const double *st_size, const int32_t *dyn_count,
+                                       const double *dyn_pos, const double *dyn_size, const double *prob,
+                                       int32_t *best_cand, int32_t *best_pos, double *scores, double *weighted,
+                                       void *stream) {
+    return impc_select::launch(ctx, p, instances, x_cand, valid, first_time, prev_states, prev_count, xref, st_centroid,
+                               st_size, nullptr, dyn_count, dyn_pos, dyn_size, prob, best_cand, best_pos, scores,
+                               weighted, stream);
 }
 
 extern "C" int impc_select_best(impc_ctx ctx, const impc_select_params *p, int64_t instances,

@@ -265,7 +265,9 @@ EXPORTED = [
     "impc_stream_wait", "impc_stream_synchronize", "impc_batch_set_values_async", "impc_batch_get_async",
     "impc_batch_update_lin_cost_device", "impc_batch_update_bounds_device", "impc_ctx_pool_stats",
     "impc_replan_create", "impc_replan_destroy", "impc_replan_set_state", "impc_replan_run", "impc_replan_get_stats",
-    "impc_replan_view_device", "impc_replan_shape", "impc_replan_advance_device", "impc_batch_follow_plan_device",
+    "impc_replan_view_device", "impc_replan_shape", "impc_replan_bind_static_count",
+    "impc_replan_shape_static", "impc_replan_static_count_device",
+    "impc_replan_advance_device", "impc_batch_follow_plan_device",
     "impc_replan_pack_device", "impc_replan_gather", "impc_replan_set_ref", "impc_replan_ref_device",  # bound in impc.replan
     "impc_replan_target_device", "impc_replan_check_device",  # bound in impc.execution
     "impc_copy_rows_device", "impc_batch_update_matrices", "impc_batch_update_matrices_device",

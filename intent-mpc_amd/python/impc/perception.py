@@ -171,9 +171,18 @@ class DeviceTick:
     zero, its SINGLE_CURRENT branch.  After the plan, target() and check() serve what the caller does
     with it (impc.execution: trajExeCB's tracking target, and mpcHasCollision / hasDynamicCollision
     against the tick's map and the gate's boxes), on the same stream.  Owns the gate's and the
-    predictor's output buffers; `replan` is an impc.replan.DeviceReplan with K = params.max_out slots."""
+    predictor's output buffers; `replan` is an impc.replan.DeviceReplan with K = params.max_out slots.
 
-    def __init__(self, ctx, replan, tracks, params, occ=None, omap=None, tp=None, ip=None, predictor=True):
+    clusters: an impc.clustering.StaticClusters over the same I vehicles with max_boxes = the replan's
+    num_static (mpcPlanner::staticObstacleClusteringCB feeding makePlanWithPred's
+    obclustering_->getStaticObstacles(), mpcPlanner.cpp:200-247, :594).  The tick then runs the
+    clustering on its map before the plan, binds the clustering's count [I] to the replan
+    (impc_replan_bind_static_count: each vehicle plans around its own s_i boxes) and hands its
+    centroid / size / yaw to the replan in place -- still nothing on the host.  map_max: the map's
+    upper corner for the clustering (default origin + dims * resolution)."""
+
+    def __init__(self, ctx, replan, tracks, params, occ=None, omap=None, tp=None, ip=None, predictor=True,
+                 clusters=None, map_max=None):
         I, K, L = replan.I, replan.K, replan.L
         if params.max_out != K:
             raise ValueError(f"DeviceTick: max_out {params.max_out} != the replan's num_obstacles {K}")
@@ -202,6 +211,21 @@ class DeviceTick:
             if self.tp.num_pred != L - 1:
                 raise ValueError("DeviceTick: the predictor's num_pred must be the replan's pred_len - 1")
             self.ip = ip if ip is not None else intent_params()
+        self.clusters = clusters
+        if clusters is not None:
+            if clusters.S != replan.S_st or clusters.I != I:
+                raise ValueError(f"DeviceTick: the clustering's max_boxes {clusters.S} / instances {clusters.I} != "
+                                 f"the replan's num_static {replan.S_st} / instances {I}")
+            if self.omap is None:
+                raise ValueError("DeviceTick: the clustering needs the occupancy map (omap, occ)")
+            m = self.omap
+            self.map_max = [float(v) for v in map_max] if map_max is not None else \
+                [m.origin[k] + m.dims[k] * m.resolution for k in range(3)]
+            replan.bind_static_count(clusters.arrays["count"].ptr)
+
+    def cluster(self, pos_ptr, vel_ptr, active=None, first=None):
+        """The static-obstacle clustering of every vehicle on the tick's map (impc_cluster_run_device)."""
+        self.clusters.run_device(pos_ptr, vel_ptr, self.omap, self.map_max, self.occ_ptr, active=active, first=first)
 
     def gather(self, pos_ptr, yaw_ptr=None):
         gather_device(self.tracks, self.params, self.I, pos_ptr, yaw_ptr, self.gate.out)
@@ -225,6 +249,9 @@ class DeviceTick:
 
     def plan(self, pos_ptr, vel_ptr, xref_ptr, **kw):
         g = self.gate
+        if self.clusters is not None:  # the clustering's boxes in place; their count is bound
+            a = self.clusters.arrays
+            kw = dict(kw, st_centroid=a["centroid"].ptr, st_size=a["size"].ptr, st_yaw=a["yaw"].ptr)
         if self.predictor:
             self.replan.run_device(pos_ptr, vel_ptr, xref_ptr, g.cur_pos.ptr, self.pred_pos.ptr, self.pred_size.ptr,
                                    self.prob.ptr, num_pred=g.num.ptr, **kw)
@@ -233,9 +260,12 @@ class DeviceTick:
                                    self.prob.ptr, has_pred=self.no_pred.ptr, cur_size=g.cur_size.ptr,
                                    cur_count=g.num.ptr, **kw)
 
-    def run_device(self, pos_ptr, vel_ptr, xref_ptr, yaw_ptr=None, **kw):
+    def run_device(self, pos_ptr, vel_ptr, xref_ptr, yaw_ptr=None, cluster_active=None, cluster_first=None, **kw):
         """The whole tick from device addresses: pos / vel [I][3], xref [I][N][8], yaw [I] (only with
-        fov < 2 pi); kw: the replan's budget (solver_time_limit, elapsed_s)."""
+        fov < 2 pi); kw: the replan's budget (solver_time_limit, elapsed_s).  With clusters:
+        cluster_active / cluster_first [I] int8 device addresses or None (impc_cluster_in)."""
+        if self.clusters is not None:
+            self.cluster(pos_ptr, vel_ptr, cluster_active, cluster_first)
         self.gather(pos_ptr, yaw_ptr)
         if self.predictor:
             self.predict()
@@ -265,6 +295,8 @@ class DeviceTick:
         return self.check_out
 
     def close(self):
+        if self.clusters is not None and self.replan.h:
+            self.replan.bind_static_count(None)  # the clustering's count array is its owner's to free
         self.gate.free()
         if self.check_out is not None:
             self.check_out.free()

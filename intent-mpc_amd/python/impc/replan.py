@@ -32,7 +32,9 @@ one grouped launch whose per-shape QP counts the device decides and the solver r
 memory -- the library call never waits for the device and reads nothing back.  With num_static
 S_st > 0 every QP not on a first plan also carries the instance's S_st static obstacles
 (obclustering_->getStaticObstacles(), :594; scored by getTrajectoryScore too) and the first plans
-move to shape K + 2.
+move to shape K + 2.  With per-instance static counts bound (impc_replan_bind_static_count: s_i of
+the S_st boxes, e.g. the device clustering's count) a shape is the pair (k, s) -- shape_id /
+shape_pair / shape_capacity below restate the ids and capacities of include/impc_replan.h.
 
 What a replan decided leaves the object as one fixed-size record per instance (ReplanRecord +
 plan states, record_dtype): impc_replan_pack_device writes them on the device and
@@ -129,6 +131,45 @@ _sig("impc_replan_shape", _P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_int64), C.
      C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P))
 
 
+_sig("impc_replan_bind_static_count", _P, _P)
+_sig("impc_replan_shape_static", _P, C.c_int32, C.c_int32, C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(_P),
+     C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P))
+_sig("impc_replan_static_count_device", _P, C.POINTER(_P))
+
+
+def num_shapes(K, S_st, bound=False):
+    """Shapes of a replan object: K + 2 by dynamic count, the first plans' K + 2 with S_st > 0, and
+    the S_st (K + 2) pairs (k, s < S_st) once static counts were bound."""
+    return K + 2 + (1 if S_st else 0) + (S_st * (K + 2) if bound and S_st else 0)
+
+
+def shape_id(K, S_st, k, s=None):
+    """The id of the shape with k dynamic (0 .. K + 1) and s static (0 .. S_st; None = S_st) rows per
+    stage: k for s = S_st, else K + 3 + s (K + 2) + k.  (The first plans' shape K + 2 is no pair.)"""
+    s = S_st if s is None else int(s)
+    if not (0 <= k <= K + 1 and 0 <= s <= S_st):
+        raise ValueError(f"shape ({k}, {s}) outside 0..{K + 1}, 0..{S_st}")
+    return int(k) if s == S_st else K + 3 + s * (K + 2) + int(k)
+
+
+def shape_pair(K, S_st, sid):
+    """(k, s) of shape id `sid`: its dynamic and static rows per stage (the first plans' K + 2: (0, 0))."""
+    if not 0 <= sid < num_shapes(K, S_st, True):
+        raise ValueError(f"shape id {sid} outside 0..{num_shapes(K, S_st, True) - 1}")
+    if sid <= K + 1:
+        return int(sid), S_st
+    if sid == K + 2:
+        return 0, 0
+    e = sid - (K + 3)
+    return e % (K + 2), e // (K + 2)
+
+
+def shape_capacity(I, K, S_st, sid):
+    """Rows shape `sid` is sized for: I (k = 0 and the first plans'), 4 I (1 <= k <= K), 2 I (K + 1)."""
+    k = shape_pair(K, S_st, sid)[0]
+    return I if (k == 0 or sid == K + 2) else 4 * I if k <= K else 2 * I
+
+
 def solve_traj_ok(info):
     """solveTraj's successSolve per solved QP (host restatement of impc_lib::solve_traj_ok,
     mpcPlanner.cpp:475-478, :513-518): initSolver succeeded (setup_exitflag 0) and solveProblem
@@ -162,10 +203,15 @@ def assemble(per_inst, shapes):
     br, K, R = per_inst["branch"], per_inst["num_obs"], per_inst["slot_row"]
     SH = per_inst.get("shape", K)
     I = br.shape[0]
+    sc, dims = per_inst.get("static_count"), per_inst.get("shape_dims")  # bound counts: ids of (k, s_i)
+
+    def sid(i, k):
+        return k if sc is None else shape_id(dims[0], dims[1], k, sc[i])
+
     out = {"inst_fanout": np.flatnonzero(br == FANOUT), "inst_first": np.flatnonzero(br == SINGLE_FIRST),
            "inst_current": np.flatnonzero(br == SINGLE_CURRENT)}
-    rows = {"single": [(int(K[i]), int(R[i, s])) for i in out["inst_fanout"] for s in range(4)],
-            "pair": [(int(K[i]) + 1, int(R[i, s])) for i in out["inst_fanout"] for s in (4, 5)],
+    rows = {"single": [(sid(i, int(K[i])), int(R[i, s])) for i in out["inst_fanout"] for s in range(4)],
+            "pair": [(sid(i, int(K[i]) + 1), int(R[i, s])) for i in out["inst_fanout"] for s in (4, 5)],
             "first": [(int(SH[i]), int(R[i, 0])) for i in out["inst_first"]],
             "current": [(int(SH[i]), int(R[i, 0])) for i in out["inst_current"]]}
     for nm in CATEGORIES:
@@ -184,7 +230,7 @@ def assemble(per_inst, shapes):
             same = key in ("x", "info", "lat") or len({k for k, _ in rr}) == 1
             out[f"{key}_{nm}"] = np.stack(parts) if same else parts
     slot = per_inst.get("cand_slot")
-    out["cand_rows"] = [[((int(K[i]) + (1 if slot[i, c] >= 4 else 0)), int(R[i, slot[i, c]])) for c in range(6)]
+    out["cand_rows"] = [[(sid(i, int(K[i]) + (1 if slot[i, c] >= 4 else 0)), int(R[i, slot[i, c]])) for c in range(6)]
                         if br[i] == FANOUT else None for i in range(I)] if slot is not None else None
     out["single_rows"] = [(int(SH[i]), int(R[i, 0])) if br[i] != FANOUT else None for i in range(I)]
     return out
@@ -216,7 +262,8 @@ class DeviceReplan:
                  num_static=0):
         self.ctx, self.params, self.pd, self.I, self.K, self.L = ctx, params, pd, int(I), int(K), int(L)
         self.S_st = int(num_static)
-        self.num_shapes = self.K + 2 + (1 if self.S_st else 0)
+        self.num_shapes = num_shapes(self.K, self.S_st)  # grows with the first bound static counts
+        self.bound = None  # the device address of the bound static counts
         self.N = params.horizon
         self.n = 13 * self.N - 5
         self.settings = settings
@@ -282,6 +329,22 @@ class DeviceReplan:
                            num_pred=num_pred, st_centroid=st_centroid, st_size=st_size, st_yaw=st_yaw)
         _check(lib.impc_replan_run(self.h, C.byref(inp)), "impc_replan_run")
 
+    def bind_static_count(self, count_ptr):
+        """impc_replan_bind_static_count: count_ptr the device address of count [I] int32 (e.g.
+        impc.clustering.StaticClusters.arrays["count"].ptr), read by every later replan; None unbinds."""
+        _check(lib.impc_replan_bind_static_count(self.h, _P(count_ptr) if count_ptr else None),
+               "impc_replan_bind_static_count")
+        self.bound = count_ptr or None
+        if count_ptr:
+            self.num_shapes = num_shapes(self.K, self.S_st, True)
+
+    def static_count(self):
+        """impc_replan_static_count_device on the host: [I], the static rows of each instance's QPs in
+        the last run."""
+        p = _P()
+        _check(lib.impc_replan_static_count_device(self.h, C.byref(p)), "impc_replan_static_count_device")
+        return _get(self.ctx, p.value, self.I, np.int32)
+
     def advance_device(self, t, pos_ptr, vel_ptr):
         """impc_replan_advance_device: pos / vel [I][3] (device) = getPos(t) / getVel(t) of every
         instance with a plan (mpc_node.cpp:216-224)."""
@@ -313,19 +376,27 @@ class DeviceReplan:
         _check(lib.impc_replan_get_stats(self.h, C.byref(s)), "impc_replan_get_stats")
         return {f: getattr(s, f) for f, _ in ReplanStats._fields_}
 
-    def shape(self, k):
+    def shape(self, k, s=None):
         """impc_replan_shape k (dynamic-obstacle count 0 .. K + 1; K + 2: the first plans with static
-        obstacles): (batch handle, QP count solved, row_inst
-        and row_code device pointers, device value pointers)."""
+        obstacles), or with s impc_replan_shape_static of the pair (k, s static rows): (batch handle,
+        QP count solved, row_inst and row_code device pointers, device value pointers)."""
         b, cnt, ri, rc = _P(), C.c_int64(), _P(), _P()
         ptrs = [_P() for _ in range(5)]
-        _check(lib.impc_replan_shape(self.h, k, C.byref(b), C.byref(cnt), C.byref(ri), C.byref(rc),
-                                     *[C.byref(p) for p in ptrs]), "impc_replan_shape")
+        if s is None:
+            _check(lib.impc_replan_shape(self.h, k, C.byref(b), C.byref(cnt), C.byref(ri), C.byref(rc),
+                                         *[C.byref(p) for p in ptrs]), "impc_replan_shape")
+        else:
+            _check(lib.impc_replan_shape_static(self.h, k, s, C.byref(b), C.byref(cnt), C.byref(ri), C.byref(rc),
+                                                *[C.byref(p) for p in ptrs]), "impc_replan_shape_static")
         return b.value, cnt.value, ri.value, rc.value, [p.value for p in ptrs]
+
+    def shape_by_id(self, sid):
+        """shape() of shape id `sid` (0 .. num_shapes - 1)."""
+        return self.shape(sid) if sid <= self.K + 2 else self.shape(*shape_pair(self.K, self.S_st, sid))
 
     def _shape_results(self, k, with_values, profile=False):
         """Host copies of shape k's last results (its solved rows) -- inspection for tests."""
-        b, cnt, ri, rc, ptrs = self.shape(k)
+        b, cnt, ri, rc, ptrs = self.shape_by_id(k)
         if not cnt:
             return None
         st = self._stats_of(b)
@@ -336,7 +407,7 @@ class DeviceReplan:
         _check(lib.impc_batch_get(_P(b), x.ctypes.data_as(C.POINTER(C.c_double)),
                                   y.ctypes.data_as(C.POINTER(C.c_double)), info.ctypes.data_as(_P)), "impc_batch_get")
         out = dict(x=x[:cnt], y=y[:cnt, :m], info=info[:cnt], row_inst=_get(self.ctx, ri, cnt, np.int32),
-                   row_code=_get(self.ctx, rc, cnt, np.int8), batch=b)
+                   row_code=_get(self.ctx, rc, cnt, np.int8), batch=b, pair=shape_pair(self.K, self.S_st, k))
         if with_values:
             out["vals"] = [_get(self.ctx, p, (cnt, ln), np.float64)
                            for p, ln in zip(ptrs, (st["nnzP"], n, st["nnzA"], m, m))]
@@ -356,14 +427,16 @@ class DeviceReplan:
 
     def run(self, pos, vel, xref, prev=None, first_time=None, prev_count=None, dyn_cur=None, pred_pos=None,
             pred_size=None, prob=None, timings=None, solver_time_limit=None, t_start=None, profile=False,
-            has_pred=None, cur_size=None, cur_count=None, values=True, num_pred=None, static=None):
+            has_pred=None, cur_size=None, cur_count=None, values=True, num_pred=None, static=None,
+            static_count=None):
         """One makePlanWithPred over all instances from host arrays (uploaded here; test plumbing
         around impc_replan_run).  Inputs: pos, vel [I][3]; xref [I][N][8] or an
         impc.ReferencePaths (getXRef on the device, from `pos`); dyn_cur [I][K][3]; pred_pos /
         pred_size [I][K][4][L][3], prob [I][K][4]; has_pred [I] (default all); num_pred [I] (K_i,
         0..K: each instance's first K_i obstacle slots; default K); cur_size [I][K][3] + cur_count [I]
         (0..K): the current dynamic obstacles a no-prediction instance keeps (default none).  static =
-        (centroid [I][S_st][3], size [I][S_st][3], yaw [I][S_st]) with num_static > 0.  prev [I][N][8] / first_time [I]: when given, the planner state is set
+        (centroid [I][S_st][3], size [I][S_st][3], yaw [I][S_st]) with num_static > 0; static_count [I]:
+        each instance's s_i, uploaded and bound for this replan (the earlier binding is restored).  prev [I][N][8] / first_time [I]: when given, the planner state is set
         from them first (impc_replan_set_state; prev_count is implied -- 0 on a first plan, N
         otherwise -- and checked when passed); else the replan continues from the committed state.
 
@@ -414,9 +487,12 @@ class DeviceReplan:
             args.update(st_centroid=dev(np.asarray(static[0]).reshape(I, S, 3)),
                         st_size=dev(np.asarray(static[1]).reshape(I, S, 3)),
                         st_yaw=dev(np.asarray(static[2]).reshape(I, S)))
+        was_bound = self.bound
+        if static_count is not None:
+            self.bind_static_count(dev(np.asarray(static_count).reshape(I), np.int32))
         self.ctx.synchronize()
         t_up = time.perf_counter() - t0
-        batches = [self.shape(k)[0] for k in range(self.num_shapes)]
+        batches = [self.shape_by_id(k)[0] for k in range(self.num_shapes)]
         if profile:
             for b in batches:
                 if b:
@@ -432,6 +508,8 @@ class DeviceReplan:
             for b in batches:
                 if b:
                     _check(lib.impc_batch_set_profiling(_P(b), 0), "impc_batch_set_profiling")
+        if static_count is not None:
+            self.bind_static_count(was_bound)
         for d in tmp:
             d.free()
         if timings is not None:
@@ -440,7 +518,9 @@ class DeviceReplan:
 
     def results(self, values=True, profile=False):
         """Host copies of the last replan's per-instance outputs (weighted [I][6]: the selection's
-        scores), state and per-shape results (test / tool inspection after the call)."""
+        scores), state and per-shape results (test / tool inspection after the call).  shapes is keyed
+        by shape id, each with pair = (k, s), its dynamic and static rows per stage; once static counts
+        were bound, static_count [I] holds the static rows of each instance's QPs."""
         I = self.I
         st = self.stats()
         v = self.view()
@@ -450,6 +530,8 @@ class DeviceReplan:
                    num_obs=_get(self.ctx, v.num_obs, I, np.int32), slot_row=_get(self.ctx, v.slot_row, (I, 6), np.int32),
                    shape=_get(self.ctx, v.shape, I, np.int32), weighted=_get(self.ctx, v.weighted, (I, 6), np.float64),
                    issued=bool(st["issued"]), time_limit=st["time_limit"])
+        if self.num_shapes > num_shapes(self.K, self.S_st):  # counts were bound: the shapes are pairs
+            out.update(static_count=self.static_count(), shape_dims=(self.K, self.S_st))
         shapes = {}
         for k in range(self.num_shapes):
             r = self._shape_results(k, values, profile)

@@ -40,7 +40,20 @@ gate, the two predictor kernels and the replan (the context's step timer), and h
 `replan` (impc_replan_check_device on the fresh plan, the tick's map and the gate's boxes) and how
 many were `done` (impc_replan_target_device one replan period into it); the two counts are also
 printed per replan on stderr.  One GPU.  The same tick
-at small I is checked replan by replan in tests/test_tick.py."""
+at small I is checked replan by replan in tests/test_tick.py.
+
+--cluster S [--out FILE]: the static-obstacle clustering in the loop (mpcPlanner::staticObstacleClusteringCB
+feeding obclustering_->getStaticObstacles(), mpcPlanner.cpp:200-247, :594).  A seeded field of pillars
+is laid over the flight (scenarios.live_loop's paths and baked predictions); per replan getXRef, ONE
+impc_cluster_run_device with at most S boxes per vehicle, ONE impc_replan_run with the clustering's
+count [I] bound (impc_replan_bind_static_count: vehicle i plans around its own s_i boxes, its QPs in
+the shapes (k, s_i)) and its centroid / size / yaw passed in place, and the vehicle following its plan.
+The same loop then runs again in the only form the replan had before counts could be bound: nothing
+bound, every vehicle carrying all S rows (the rows past its count are the boxes it held earlier, or
+zero-size boxes at the origin).  One JSON line: replans/s of both, the distribution of s_i per replan,
+and the device memory of the replan object in both forms (the sum of its solver batches' device bytes;
+the bound object holds S + 1 times the shapes).  One GPU.  --out also appends the line to FILE.
+The same chain at small I is checked against the restatement in tests/test_replan_static_counts.py."""
 import argparse
 import json
 import os
@@ -162,6 +175,129 @@ def detector_loop(a):
     ctx.close()
 
 
+def pillar_field(paths, advance_m, seed, res=0.2, clear=0.9):
+    """An inflated occupancy grid over the first advance_m metres of every path: pillars of 0.4-1.0 m
+    on a jittered 3 m grid over the map's whole height.  Returns (map dict, map_max, occ uint8 [x][y][z])."""
+    first = np.concatenate([np.asarray(p, np.float64).reshape(-1, 3)[:2] for p in paths])
+    lo = np.floor(first.min(axis=0) - [advance_m + 8.0, advance_m + 8.0, 0.0])
+    hi = np.ceil(first.max(axis=0) + [advance_m + 8.0, advance_m + 8.0, 0.0])
+    lo[2], hi[2] = np.floor(first[:, 2].min() - 3.0), np.ceil(first[:, 2].max() + 3.0)
+    dims = np.round((hi - lo) / res).astype(int)
+    occ = np.zeros(dims, np.uint8)
+    rng = np.random.default_rng(seed)
+    for gx in np.arange(lo[0] + 1.5, hi[0] - 1.5, 3.0):
+        for gy in np.arange(lo[1] + 1.5, hi[1] - 1.5, 3.0):
+            if rng.random() < 0.45:
+                continue
+            c = np.array([gx, gy]) + rng.uniform(-0.9, 0.9, 2)
+            h = rng.uniform(0.2, 0.5, 2)
+            a = np.maximum(np.floor((c - h - lo[:2]) / res).astype(int), 0)
+            b = np.minimum(np.ceil((c + h - lo[:2]) / res).astype(int), dims[:2])
+            occ[a[0]:b[0], a[1]:b[1], :] = 1
+    # a corridor of `clear` m around every path stays free: the vehicles fly between the pillars
+    r = int(np.ceil(clear / res))
+    free = np.zeros(dims[:2], bool)
+    for p in paths:
+        pts = np.asarray(p, np.float64).reshape(-1, 3)[:, :2]
+        seg = np.concatenate([np.linspace(pts[k], pts[k + 1], 8, endpoint=False) for k in range(len(pts) - 1)])
+        ij = np.floor((seg - lo[:2]) / res).astype(int)
+        ij = ij[((ij >= 0) & (ij < dims[:2])).all(axis=1)]
+        free[ij[:, 0], ij[:, 1]] = True
+    grown = np.zeros_like(free)
+    for dx in range(-r, r + 1):
+        for dy in range(-r, r + 1):
+            if dx * dx + dy * dy <= r * r:
+                grown |= np.roll(np.roll(free, dx, axis=0), dy, axis=1)
+    occ[grown] = 0
+    m = dict(origin=lo.tolist(), res=res, dims=dims.tolist())
+    return m, (lo + dims * res).tolist(), occ
+
+
+def cluster_loop(a):
+    import impc
+    from impc import clustering as CL
+    from impc import perception as P
+    from impc import scenarios
+    from impc.replan import DeviceReplan
+    I, K, R, N, S = a.instances, a.obstacles, a.replans, a.horizon, a.cluster
+    t0 = time.time()
+    sc = scenarios.live_loop(I, K, R, N=N, seed=4100)
+    m, map_max, occ = pillar_field(sc["paths"], 0.5 * R, 4103)
+    gen_s = time.time() - t0
+    p, pd, L = sc["params"], sc["pd"], sc["L"]
+    ctx = impc.Context(0)
+    Dv = impc.DeviceArray
+    c = np.ascontiguousarray
+    omap = P.occ_map(m["origin"], m["res"], m["dims"])
+    occ_d = Dv(ctx, c(occ).reshape(-1))
+    psize_d, prob_d = Dv(ctx, c(sc["pred_size"])), Dv(ctx, c(sc["prob"]))
+    pred_d, cur_d = Dv(ctx, c(sc["pred_pos"])), Dv(ctx, c(sc["dyn_cur"]))
+    step_pred, step_cur = pred_d.nbytes // R, cur_d.nbytes // R
+    paths = impc.ReferencePaths(ctx, list(sc["paths"]), pd["ts"], N)
+    cpar = CL.cluster_params(**CL.LIVE_PARAMS, max_points=a.cluster_points, max_boxes=S)
+
+    def run(bound):
+        rp = DeviceReplan(ctx, p, pd, I, K, L, impc.default_settings(verbose=0), num_static=S)
+        cl = CL.StaticClusters(ctx, cpar, I)
+        if bound:
+            rp.bind_static_count(cl.arrays["count"].ptr)
+        mem = sum(rp._stats_of(rp.shape_by_id(k)[0])["device_bytes"] for k in range(rp.num_shapes))
+        pos_d, vel_d, xref_d = Dv(ctx, c(sc["pos0"])), Dv(ctx, c(sc["vel0"])), Dv(ctx, (I, N, 8))
+        ar = cl.arrays
+        walls, hist, flags, branches = [], [], [], []
+        for r in range(R):
+            ctx.synchronize()
+            t = time.perf_counter()
+            paths.xref_device(pos_d.ptr, xref_d.ptr)
+            cl.run_device(pos_d.ptr, vel_d.ptr, omap, map_max, occ_d.ptr)
+            rp.run_device(pos_d.ptr, vel_d.ptr, xref_d.ptr, cur_d.ptr + r * step_cur, pred_d.ptr + r * step_pred,
+                          psize_d.ptr, prob_d.ptr, st_centroid=ar["centroid"].ptr, st_size=ar["size"].ptr,
+                          st_yaw=ar["yaw"].ptr)
+            rp.advance_device(pd["ts"], pos_d.ptr, vel_d.ptr)
+            ctx.synchronize()
+            walls.append(time.perf_counter() - t)
+            hist.append(np.bincount(ar["count"].get(), minlength=S + 1).tolist())
+            flags.append(int((ar["flags"].get() != 0).sum()))
+            st = rp.stats()
+            branches.append([int(st["fanout"]), int(st["single_first"]), int(st["single_current"])])
+        last = rp.results(values=False)
+        its = np.concatenate([s["info"]["iter"] for s in last["shapes"].values()])
+        valid = int(rp.plans()[3].sum())
+        fan = np.array(walls)[1:]
+        out = {"replans_per_s": float(I / np.median(fan)), "fanout_replan_s_median": float(np.median(fan)),
+               "first_replan_s": float(walls[0]), "fanout_replan_s": fan.tolist(), "replan_device_bytes": int(mem),
+               "shapes": rp.num_shapes, "shapes_used_last": len(last["shapes"]), "branches": branches,
+               "static_count_hist": hist, "cluster_flagged": flags, "qps_last": int(its.size),
+               "mean_iter_last": float(its.mean()), "valid_plans": valid}
+        if bound:
+            rp.bind_static_count(None)
+        for d in (pos_d, vel_d, xref_d):
+            d.free()
+        cl.close()
+        rp.close()
+        return out
+
+    bound, fixed = run(True), run(False)
+    line = json.dumps({
+        "workload": f"live loop with the static-obstacle clustering: {I} instances on ref_trajectory_dynus_benchmark.txt, "
+                    f"N={N}, K={K} dynamic obstacles, a pillar field of {int(occ.any(axis=2).sum())} occupied columns "
+                    f"({m['res']} m voxels), at most {S} boxes per vehicle, {R} chained replans (getXRef + clustering + "
+                    f"makePlanWithPred + follow plan 0.1 s per replan)",
+        "instances": I, "replans": R, "n_gpus": 1, "num_static": S,
+        "bound_counts": bound, "fixed_num_static": fixed,
+        "memory_ratio": bound["replan_device_bytes"] / max(fixed["replan_device_bytes"], 1),
+        "gen_s": gen_s, "build_id": impc.lib.impc_build_id().decode()})
+    print(line, flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+    for d in (occ_d, psize_d, prob_d, pred_d, cur_d):
+        d.free()
+    paths.close()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--instances", type=int, default=8192)
@@ -177,7 +313,15 @@ def main():
     ap.add_argument("--range", type=float, default=30.0, help="--detector: sensor range (color_distance)")
     ap.add_argument("--hist", type=int, default=100, help="--detector: history entries per track (history_size)")
     ap.add_argument("--world-obstacles", type=int, default=8, help="--detector: obstacles M in every instance's world")
+    ap.add_argument("--cluster", type=int, default=0,
+                    help="clustering every tick, at most this many boxes per vehicle, counts bound to the replan")
+    ap.add_argument("--cluster-points", type=int, default=2048, help="--cluster: max_points of the clustering")
+    ap.add_argument("--out", default=None, help="--cluster: also append the JSON line to this file")
     a = ap.parse_args()
+    if a.cluster:
+        if a.gpus != 1 or a.mixed_k or a.statics or a.detector:
+            sys.exit("live_loop.py: --cluster runs on one GPU, without --mixed-k / --statics / --detector")
+        return cluster_loop(a)
     if a.detector:
         if a.gpus != 1 or a.mixed_k or a.statics:
             sys.exit("live_loop.py: --detector runs on one GPU, without --mixed-k / --statics")
