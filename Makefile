@@ -1,6 +1,8 @@
 # Builds (all in-tree so the .so files travel to the GPU box with the snapshot):
 #   intent-mpc_amd/lib/libimpc_qp.so      product: HIP kernels (gfx950) + C-ABI + host symbolic
-#                                         analysis + MPC->QP builder
+#                                         analysis + MPC->QP builder; one translation unit per
+#                                         module of intent-mpc_amd/csrc (*.hip, *.cpp), each rebuilt
+#                                         only when a file it includes changes
 #   oracle/build/libosqp_oracle.so        test oracle: C restatement of OSQP 0.6.2 (gcc)
 #   tests/native/build/libimpc_core_cpu.so test-only CPU build of admm_core.hpp (debug harness)
 HIPCC   ?= /opt/rocm/bin/hipcc
@@ -20,11 +22,19 @@ HOSTFLAGS := -O2 -std=c++17 -fPIC -ffp-contract=off -Wall
 # RCCL (multi-GPU cost all-gather, include/impc_comm.h), from the same ROCm as the HIP runtime
 LDLIBS    := -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
-# build identity baked into the library (impc_build_id): every source compiled into it + the flags
+# build identity baked into the library (impc_build_id, csrc/build_id.cpp): every source compiled into
+# it + the flags.  Only the id unit takes it, so only the id unit is rebuilt for every source change.
 SRCS    := $(sort $(wildcard $(CSRC)/*.hip $(CSRC)/*.hpp $(CSRC)/*.cpp $(ROOT)/include/*.h))
 BUILD_ID := src-$(shell cat $(SRCS) | { cat; echo '$(HIPFLAGS) $(HOSTFLAGS)'; } | sha256sum | cut -c1-16)
 GIT_REV := $(shell git -C $(ROOT) rev-parse --short HEAD 2>/dev/null || echo unknown)
 IDFLAGS  = -DIMPC_BUILD_ID='"$(BUILD_ID)$(1)"' -DIMPC_GIT_REV='"$(GIT_REV)"'
+
+# the library: one object per csrc/*.hip (device + host) and per csrc/*.cpp (host).  SOLVER is the
+# structured and generic solver's unit (minutes to compile); REST is every other object.
+OBJS    := $(patsubst $(CSRC)/%,$(LIBDIR)/%.o,$(basename $(filter %.hip %.cpp,$(SRCS))))
+SOLVER  := $(LIBDIR)/impc_qp.o
+REST    := $(filter-out $(SOLVER) $(LIBDIR)/build_id.o,$(OBJS))
+LINK     = $(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $^ -o $@ $(LDLIBS)
 
 LIB     := $(LIBDIR)/libimpc_qp.so
 PROFLIB := $(LIBDIR)/libimpc_qp_prof.so
@@ -46,51 +56,40 @@ lib: $(LIB)
 oracle: $(ORACLE)
 harness: $(HARNESS) $(EMU) $(EMU64) $(SHIMT) $(REPLANX) $(DETECTH) $(EXECH) $(MFMODEL) $(STMODEL) $(CLUSTH)
 
-# (every source and header of the library: the build identity above is taken over the same list)
-$(LIBDIR)/impc_qp.o: $(CSRC)/impc_qp.hip $(SRCS)
+# each unit depends on what it includes, as the compiler reports it (lib/*.d)
+$(LIBDIR)/%.o: $(CSRC)/%.hip
 	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) $(call IDFLAGS,) -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) -MMD -MP -c $< -o $@
+$(LIBDIR)/%.o: $(CSRC)/%.cpp
+	@mkdir -p $(LIBDIR)
+	$(CXX) $(HOSTFLAGS) -MMD -MP -c $< -o $@
+-include $(wildcard $(LIBDIR)/*.d)
 
-# section-profiling variant of the library (tools/section_profile.py; never the product)
+# the id unit, per library: build_id.o for the product, build_id_<name>.o with the id suffix -<name>
+$(LIBDIR)/build_id.o: $(CSRC)/build_id.cpp $(SRCS)
+	@mkdir -p $(LIBDIR)
+	$(CXX) $(HOSTFLAGS) $(call IDFLAGS,) -c $< -o $@
+$(LIBDIR)/build_id_%.o: $(CSRC)/build_id.cpp $(SRCS)
+	@mkdir -p $(LIBDIR)
+	$(CXX) $(HOSTFLAGS) $(call IDFLAGS,-$*) -c $< -o $@
+
+$(LIB): $(SOLVER) $(LIBDIR)/build_id.o $(REST)
+	$(LINK)
+
+# section-profiling variant of the library (tools/section_profile.py; never the product): the solver
+# unit with the extra define, every other object as it is
 prof: $(PROFLIB)
-$(LIBDIR)/impc_qp_prof.o: $(CSRC)/impc_qp.hip $(SRCS)
+$(LIBDIR)/impc_qp_prof.o: $(CSRC)/impc_qp.hip
 	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) $(call IDFLAGS,-prof) -DIMPC_SECTION_PROF -c $< -o $@
-$(PROFLIB): $(LIBDIR)/impc_qp_prof.o $(LIBDIR)/replan_run.o $(LIBDIR)/cluster.o $(LIBDIR)/symbolic.o $(LIBDIR)/mpc_qp.o $(LIBDIR)/mpc_structure.o $(LIBDIR)/minsnap.o
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $^ -o $@ $(LDLIBS)
+	$(HIPCC) $(HIPFLAGS) -MMD -MP -DIMPC_SECTION_PROF -c $< -o $@
+$(PROFLIB): $(LIBDIR)/impc_qp_prof.o $(LIBDIR)/build_id_prof.o $(REST)
+	$(LINK)
 
-# the batched makePlanWithPred (include/impc_replan.h impc_replan_*): host orchestration + small
-# kernels over the library's own entry points
-$(LIBDIR)/replan_run.o: $(CSRC)/replan_run.hip $(CSRC)/lib_internal.hpp $(ROOT)/include/impc_replan.h \
-		$(ROOT)/include/impc_qp.h $(ROOT)/include/impc_mpc.h $(ROOT)/include/impc_fanout.h $(ROOT)/include/impc_select.h \
-		$(ROOT)/include/impc_comm.h $(ROOT)/include/impc_exec.h $(ROOT)/include/impc_predict.h $(CSRC)/plan_exec.hpp
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# the static-obstacle producer (include/impc_cluster.h): region scan, DBSCAN, 2-means tree, boxes
-$(LIBDIR)/cluster.o: $(CSRC)/cluster.hip $(CSRC)/cluster.hpp $(CSRC)/lib_internal.hpp $(ROOT)/include/impc_cluster.h \
-		$(ROOT)/include/impc_qp.h $(ROOT)/include/impc_predict.h $(ROOT)/include/impc_mpc.h $(ROOT)/include/impc_comm.h
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/symbolic.o: $(CSRC)/symbolic.cpp $(CSRC)/symbolic.hpp
-	@mkdir -p $(LIBDIR)
-	$(CXX) $(HOSTFLAGS) -c $< -o $@
-
-$(LIBDIR)/minsnap.o: $(CSRC)/minsnap.cpp $(ROOT)/include/impc_minsnap.h $(ROOT)/include/impc_mpc.h
-	@mkdir -p $(LIBDIR)
-	$(CXX) $(HOSTFLAGS) -c $< -o $@
-
-$(LIBDIR)/mpc_qp.o: $(CSRC)/mpc_qp.cpp $(CSRC)/mpc_qp_internal.hpp $(ROOT)/include/impc_mpc.h
-	@mkdir -p $(LIBDIR)
-	$(CXX) $(HOSTFLAGS) -c $< -o $@
-
-$(LIBDIR)/mpc_structure.o: $(CSRC)/mpc_structure.cpp $(CSRC)/mpc_structure.hpp
-	@mkdir -p $(LIBDIR)
-	$(CXX) $(HOSTFLAGS) -c $< -o $@
-
-$(LIB): $(LIBDIR)/impc_qp.o $(LIBDIR)/replan_run.o $(LIBDIR)/cluster.o $(LIBDIR)/symbolic.o $(LIBDIR)/mpc_qp.o $(LIBDIR)/mpc_structure.o $(LIBDIR)/minsnap.o
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $^ -o $@ $(LDLIBS)
+# kernel experiments (tools/ only): make variant V=name DEFS="-DX=1" -> lib/libimpc_qp_<name>.so,
+# selected at run time with IMPC_LIB_VARIANT=<name>; the solver unit is compiled on every call
+variant: $(LIBDIR)/build_id_$(V).o $(REST)
+	$(HIPCC) $(HIPFLAGS) $(DEFS) -c $(CSRC)/impc_qp.hip -o $(LIBDIR)/impc_qp_$(V).o
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $(LIBDIR)/impc_qp_$(V).o $^ -o $(LIBDIR)/libimpc_qp_$(V).so $(LDLIBS)
 
 $(ORACLE): $(ROOT)/oracle/osqp_oracle.c
 	@mkdir -p $(ORADIR)
@@ -154,12 +153,6 @@ $(MFMODEL): $(ROOT)/tests/native/sweep_mfma_model.cpp $(CSRC)/sweep_mfma_map.hpp
 $(STMODEL): $(ROOT)/tests/native/sweep_store_model.cpp $(CSRC)/sweep_mfma_map.hpp
 	@mkdir -p $(HARNDIR)
 	$(CXX) -O1 -g -std=c++17 -Wall -ffp-contract=off $(SAN) $< -o $@
-
-# kernel experiments (tools/ only): make variant V=name DEFS="-DX=1" -> lib/libimpc_qp_<name>.so,
-# selected at run time with IMPC_LIB_VARIANT=<name>
-variant: $(LIBDIR)/replan_run.o $(LIBDIR)/cluster.o $(LIBDIR)/symbolic.o $(LIBDIR)/mpc_qp.o $(LIBDIR)/mpc_structure.o $(LIBDIR)/minsnap.o
-	$(HIPCC) $(HIPFLAGS) $(call IDFLAGS,-$(V)) $(DEFS) -c $(CSRC)/impc_qp.hip -o $(LIBDIR)/impc_qp_$(V).o
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $(LIBDIR)/impc_qp_$(V).o $^ -o $(LIBDIR)/libimpc_qp_$(V).so $(LDLIBS)
 
 clean:
 	rm -rf $(LIBDIR) $(ORADIR) $(HARNDIR)

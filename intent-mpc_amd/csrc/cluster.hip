@@ -25,13 +25,6 @@
 #include "cluster.hpp"
 #include "lib_internal.hpp"
 
-#define CL_HIP(expr)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess)                                                                               \
-            return impc_lib::set_error(IMPC_DEVICE_ERROR, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 namespace impc_clu {
 
 constexpr int kThreads = 256, kWaves = kThreads / 64;
@@ -582,14 +575,14 @@ extern "C" int impc_cluster_create(impc_ctx ctx, const impc_cluster_params *p, i
     const int64_t cells = (int64_t)lay.capx * lay.capy * lay.capz;
     if (cells > (1 << 26)) return fail("impc_cluster_create: the region's lattice has more than 2^26 cells");
 
-    CL_HIP(hipSetDevice(impc_lib::device(ctx)));
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
     int lds_max = 0;
-    CL_HIP(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, impc_lib::device(ctx)));
+    HIP_OK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, impc_lib::device(ctx)));
     if (lay.total() > (size_t)lds_max)
         return fail("impc_cluster_create: max_points " + std::to_string(lay.P) + " and max_boxes " + std::to_string(lay.S) +
                     " need " + std::to_string(lay.total()) + " bytes of shared memory per workgroup, the device has " +
                     std::to_string(lds_max));
-    CL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_cluster), hipFuncAttributeMaxDynamicSharedMemorySize,
+    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_cluster), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)lay.total()));
     impc_cluster_s *c = new impc_cluster_s{};
     c->ctx = ctx, c->pr = *p, c->lay = lay, c->I = instances, c->cells = cells;
@@ -629,15 +622,15 @@ extern "C" int impc_cluster_run_device(impc_cluster c, const impc_cluster_in *in
         return fail("impc_cluster_run_device: a required array is null");
     if (!(in->map.resolution > 0) || in->map.dims[0] < 1 || in->map.dims[1] < 1 || in->map.dims[2] < 1)
         return fail("impc_cluster_run_device: the map needs a positive resolution and positive dimensions");
-    CL_HIP(hipSetDevice(impc_lib::device(c->ctx)));
+    HIP_OK(hipSetDevice(impc_lib::device(c->ctx)));
     hipStream_t st = stream ? (hipStream_t)stream : impc_lib::stream(c->ctx);
-    CL_HIP(hipStreamWaitEvent(st, c->last, 0));
+    HIP_OK(hipStreamWaitEvent(st, c->last, 0));
     Args a;
     a.pr = c->pr, a.in = *in, a.out = *out, a.lay = c->lay, a.I = c->I, a.cells = c->cells;
     a.cellmap = c->cellmap, a.angles = c->angles, a.r2max = c->r2max;
     hipLaunchKernelGGL(k_cluster, dim3(c->grid), dim3(kThreads), c->lay.total(), st, a);
-    CL_HIP(hipGetLastError());
-    CL_HIP(hipEventRecord(c->last, st));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(c->last, st));
     return IMPC_OK;
 }
 
@@ -648,7 +641,7 @@ extern "C" int impc_cluster_run(impc_cluster c, const impc_cluster_in *in, const
         return fail("impc_cluster_run: a required array is null");
     if (!(in->map.resolution > 0) || in->map.dims[0] < 1 || in->map.dims[1] < 1 || in->map.dims[2] < 1)
         return fail("impc_cluster_run: the map needs a positive resolution and positive dimensions");
-    CL_HIP(hipSetDevice(impc_lib::device(c->ctx)));
+    HIP_OK(hipSetDevice(impc_lib::device(c->ctx)));
     hipStream_t st = impc_lib::stream(c->ctx);
     const size_t I = (size_t)c->I, P = (size_t)c->pr.max_points, S = (size_t)c->pr.max_boxes;
     struct Buf {

@@ -1,13 +1,20 @@
-// detect.hpp -- the detector's track store and range gate (include/impc_detect.h), included by
-// impc_qp.hip.  The gate is one wavefront per planning instance: the lanes stride over the world's
+// detect.hip -- the detector's track store and range gate (include/impc_detect.h), its own
+// translation unit of libimpc_qp.so.  The gate is one wavefront per planning instance: the lanes stride over the world's
 // obstacles 64 at a time, each chunk takes one 64-bit ballot of the in-range predicate, a kept
 // lane's slot is the running base plus the popcount of the ballot below it (an ordered compaction,
 // no atomics, no LDS), and the whole wavefront then copies each kept track's history out of the
 // ring, newest first, with coalesced loads and stores, and zero-fills the empty slots.  The kernels
 // move bytes (a few K H 48-byte rows per instance): memory-bound and small next to the solve.
-#pragma once
+#include <hip/hip_runtime.h>
 
+#include <cmath>
+#include <string>
+
+#include "../../include/impc_detect.h"
 #include "detect_gate.hpp"
+#include "lib_internal.hpp"
+
+using impc_lib::set_error;
 
 struct impc_tracks_s {
     impc_ctx ctx = nullptr;
@@ -113,11 +120,11 @@ __global__ __launch_bounds__(64) void k_gate(GateArgs a) {
 }  // namespace impc_detect
 
 extern "C" int impc_tracks_create(impc_ctx ctx, int64_t worlds, int32_t M, int32_t H, impc_tracks *out) {
-    if (!ctx || !out) return fail(IMPC_INVALID_ARGUMENT, "tracks: null context or output");
-    if (worlds < 1 || M < 1 || H < 1) return fail(IMPC_INVALID_ARGUMENT, "tracks: worlds >= 1, M >= 1, H >= 1");
+    if (!ctx || !out) return set_error(IMPC_INVALID_ARGUMENT, "tracks: null context or output");
+    if (worlds < 1 || M < 1 || H < 1) return set_error(IMPC_INVALID_ARGUMENT, "tracks: worlds >= 1, M >= 1, H >= 1");
     if (worlds > ((int64_t)1 << 24) || (double)worlds * M * H * 24.0 > 6.4e10)
-        return fail(IMPC_INVALID_ARGUMENT, "tracks: worlds <= 2^24 and at most 64 GB of history per array");
-    HIP_OK(hipSetDevice(ctx->device));
+        return set_error(IMPC_INVALID_ARGUMENT, "tracks: worlds <= 2^24 and at most 64 GB of history per array");
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
     impc_tracks tr = new impc_tracks_s;
     tr->ctx = ctx;
     tr->worlds = worlds;
@@ -126,12 +133,12 @@ extern "C" int impc_tracks_create(impc_ctx ctx, int64_t worlds, int32_t M, int32
     const size_t bytes = sizeof(double) * 3 * (size_t)worlds * M * H;
     char *buf = nullptr;
     hipError_t e = hipMalloc((void **)&buf, 3 * bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(buf, 0, 3 * bytes, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(buf, 0, 3 * bytes, impc_lib::stream(ctx));
+    if (e == hipSuccess) e = hipStreamSynchronize(impc_lib::stream(ctx));
     if (e != hipSuccess) {
         if (buf) (void)hipFree(buf);
         delete tr;
-        return fail(IMPC_DEVICE_ERROR, std::string("tracks: allocation: ") + hipGetErrorString(e));
+        return set_error(IMPC_DEVICE_ERROR, std::string("tracks: allocation: ") + hipGetErrorString(e));
     }
     tr->pos = (double *)buf;
     tr->vel = (double *)(buf + bytes);
@@ -142,24 +149,24 @@ extern "C" int impc_tracks_create(impc_ctx ctx, int64_t worlds, int32_t M, int32
 
 extern "C" int impc_tracks_destroy(impc_tracks tr) {
     if (!tr) return IMPC_OK;
-    (void)hipSetDevice(tr->ctx->device);
-    (void)hipStreamSynchronize(tr->ctx->stream);
+    (void)hipSetDevice(impc_lib::device(tr->ctx));
+    (void)hipStreamSynchronize(impc_lib::stream(tr->ctx));
     (void)hipFree(tr->pos);  // one allocation: pos, vel, size
     delete tr;
     return IMPC_OK;
 }
 
 extern "C" int impc_tracks_reset(impc_tracks tr) {
-    if (!tr) return fail(IMPC_INVALID_ARGUMENT, "null tracks");
+    if (!tr) return set_error(IMPC_INVALID_ARGUMENT, "null tracks");
     tr->head = tr->len = 0;
     return IMPC_OK;
 }
 
 extern "C" int impc_tracks_push_device(impc_tracks tr, const double *pos, const double *vel, const double *size,
                                        void *stream) {
-    if (!tr || !pos || !vel || !size) return fail(IMPC_INVALID_ARGUMENT, "tracks push: null argument");
-    HIP_OK(hipSetDevice(tr->ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : tr->ctx->stream;
+    if (!tr || !pos || !vel || !size) return set_error(IMPC_INVALID_ARGUMENT, "tracks push: null argument");
+    HIP_OK(hipSetDevice(impc_lib::device(tr->ctx)));
+    hipStream_t st = stream ? (hipStream_t)stream : impc_lib::stream(tr->ctx);
     const int head = tr->head == 0 ? tr->H - 1 : tr->head - 1;  // push_front; at H entries it lands on the oldest
     const int64_t total3 = tr->worlds * tr->M * 3;
     hipLaunchKernelGGL(impc_detect::k_push, dim3((unsigned)((total3 + 255) / 256)), dim3(256), 0, st, total3, tr->H,
@@ -172,13 +179,13 @@ extern "C" int impc_tracks_push_device(impc_tracks tr, const double *pos, const 
 
 static int detect_check(impc_tracks tr, const impc_detect_params *p, int64_t I, const double *robot_pos,
                         const double *robot_yaw, const impc_detect_out *out) {
-    if (!tr || !p || !out) return fail(IMPC_INVALID_ARGUMENT, "detect: null tracks, parameters or outputs");
-    if (p->max_out < 1) return fail(IMPC_INVALID_ARGUMENT, "detect: max_out >= 1");
-    if (I < 0 || I > ((int64_t)1 << 24)) return fail(IMPC_INVALID_ARGUMENT, "detect: 0 <= instances <= 2^24");
+    if (!tr || !p || !out) return set_error(IMPC_INVALID_ARGUMENT, "detect: null tracks, parameters or outputs");
+    if (p->max_out < 1) return set_error(IMPC_INVALID_ARGUMENT, "detect: max_out >= 1");
+    if (I < 0 || I > ((int64_t)1 << 24)) return set_error(IMPC_INVALID_ARGUMENT, "detect: 0 <= instances <= 2^24");
     if (tr->worlds != 1 && I != tr->worlds)
-        return fail(IMPC_INVALID_ARGUMENT, "detect: instances must equal the store's worlds (or worlds = 1)");
-    if (!(p->fov >= 2 * M_PI) && !robot_yaw) return fail(IMPC_INVALID_ARGUMENT, "detect: fov < 2 pi needs robot_yaw");
-    if (I > 0 && (!robot_pos || !out->num)) return fail(IMPC_INVALID_ARGUMENT, "detect: robot_pos and out.num are required");
+        return set_error(IMPC_INVALID_ARGUMENT, "detect: instances must equal the store's worlds (or worlds = 1)");
+    if (!(p->fov >= 2 * M_PI) && !robot_yaw) return set_error(IMPC_INVALID_ARGUMENT, "detect: fov < 2 pi needs robot_yaw");
+    if (I > 0 && (!robot_pos || !out->num)) return set_error(IMPC_INVALID_ARGUMENT, "detect: robot_pos and out.num are required");
     return IMPC_OK;
 }
 
@@ -187,8 +194,8 @@ extern "C" int impc_detect_gather_device(impc_tracks tr, const impc_detect_param
                                          const impc_detect_out *out, void *stream) {
     IMPC_TRY(detect_check(tr, p, I, robot_pos, robot_yaw, out));
     if (I == 0) return IMPC_OK;
-    HIP_OK(hipSetDevice(tr->ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : tr->ctx->stream;
+    HIP_OK(hipSetDevice(impc_lib::device(tr->ctx)));
+    hipStream_t st = stream ? (hipStream_t)stream : impc_lib::stream(tr->ctx);
     impc_detect::GateArgs a{*p, *out, tr->worlds, tr->M, tr->H, tr->head, tr->len, tr->pos, tr->vel, tr->size,
                             robot_pos, robot_yaw};
     hipLaunchKernelGGL(impc_detect::k_gate, dim3((unsigned)I), dim3(64), 0, st, a);
@@ -200,8 +207,8 @@ extern "C" int impc_detect_gather(impc_tracks tr, const impc_detect_params *p, i
                                   const double *robot_yaw, const impc_detect_out *out) {
     IMPC_TRY(detect_check(tr, p, I, robot_pos, robot_yaw, out));
     if (I == 0) return IMPC_OK;
-    HIP_OK(hipSetDevice(tr->ctx->device));
-    hipStream_t st = tr->ctx->stream;
+    HIP_OK(hipSetDevice(impc_lib::device(tr->ctx)));
+    hipStream_t st = impc_lib::stream(tr->ctx);
     const size_t K = (size_t)p->max_out, IK = (size_t)I * K, H3 = (size_t)tr->H * 3;
     // device copies of the inputs and of every output asked for, in one allocation
     struct Part {
@@ -223,15 +230,15 @@ extern "C" int impc_detect_gather(impc_tracks tr, const impc_detect_params *p, i
     auto dev = [&](int k) { return parts[k].host ? (void *)(buf + parts[k].at) : nullptr; };
     impc_detect_out d{(int32_t *)dev(0), (int32_t *)dev(1), (int32_t *)dev(2), (int32_t *)dev(3), (double *)dev(4),
                       (double *)dev(5),  (double *)dev(6),  (double *)dev(7),  (double *)dev(8)};
-    int rc = h2d_sync(st, dpos, robot_pos, 24 * (size_t)I);
-    if (!rc && robot_yaw) rc = h2d_sync(st, dyaw, robot_yaw, 8 * (size_t)I);
+    int rc = impc_lib::h2d_sync(st, dpos, robot_pos, 24 * (size_t)I);
+    if (!rc && robot_yaw) rc = impc_lib::h2d_sync(st, dyaw, robot_yaw, 8 * (size_t)I);
     if (!rc) rc = impc_detect_gather_device(tr, p, I, dpos, dyaw, &d, nullptr);
     if (!rc) {
         hipError_t e = hipSuccess;
         for (int k = 0; k < 9 && e == hipSuccess; k++)
             if (parts[k].host) e = hipMemcpyAsync(parts[k].host, buf + parts[k].at, parts[k].bytes, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(IMPC_DEVICE_ERROR, std::string("detect download: ") + hipGetErrorString(e));
+        if (e != hipSuccess) rc = set_error(IMPC_DEVICE_ERROR, std::string("detect download: ") + hipGetErrorString(e));
     }
     (void)hipFree(buf);
     return rc;

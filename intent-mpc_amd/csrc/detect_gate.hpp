@@ -1,5 +1,5 @@
 // detect_gate.hpp -- fakeDetector::isObstacleInSensorRange (fakeDetector.cpp:482-500) as one
-// host / device function, term for term, so the gate kernel (detect.hpp) and a CPU harness
+// host / device function, term for term, so the gate kernel (detect.hip) and a CPU harness
 // (tests/native/detect_harness.cpp) compile the same statements.
 #pragma once
 #include <math.h>

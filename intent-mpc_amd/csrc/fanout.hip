@@ -1,5 +1,5 @@
-// fanout.hpp -- the intent-hypothesis fan-out of a replan (include/impc_fanout.h), included by
-// impc_qp.hip (same translation unit: shares the context type and error plumbing).
+// fanout.hip -- the intent-hypothesis fan-out of a replan (include/impc_fanout.h), its own
+// translation unit of libimpc_qp.so (the context and the error plumbing through lib_internal.hpp).
 //
 // Two kernels on the context stream:
 //   k_fanout_pick  one thread per instance: findClosestObstacle (mpcPlanner.cpp:663-708), the
@@ -9,7 +9,15 @@
 //   k_fanout_copy  one thread per (instance, candidate, obstacle, step): gathers the predicted
 //                  position / size rows into the builder's [nb][K'][L][3] layouts -- the bulk of
 //                  the bytes, written coalesced
-#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+
+#include "../../include/impc_fanout.h"
+#include "lib_internal.hpp"
+
+using impc_lib::set_error;
 
 namespace impc_fanout {
 
@@ -183,17 +191,17 @@ extern "C" int impc_fanout_candidates_device(impc_ctx ctx, int64_t instances, in
                                              const double *pair_size, const double *x_single, int64_t n_single,
                                              const double *x_pair, int64_t n_pair, const double **x_cand,
                                              int32_t *dyn_count, double *dyn_pos, double *dyn_size, void *stream) {
-    if (!ctx) return fail(IMPC_INVALID_ARGUMENT, "null context");
+    if (!ctx) return set_error(IMPC_INVALID_ARGUMENT, "null context");
     if (instances < 0 || num_obstacles < 1 || pred_len < 1 || n_single < 1 || n_pair < 1)
-        return fail(IMPC_INVALID_ARGUMENT, "fanout candidates: bad sizes");
+        return set_error(IMPC_INVALID_ARGUMENT, "fanout candidates: bad sizes");
     if (instances == 0) return IMPC_OK;
     if (!cand_slot || !single_pos || !single_size || !pair_pos || !pair_size || !x_single || !x_pair || !x_cand ||
         !dyn_count || !dyn_pos || !dyn_size)
-        return fail(IMPC_INVALID_ARGUMENT, "fanout candidates: null argument");
-    HIP_OK(hipSetDevice(ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+        return set_error(IMPC_INVALID_ARGUMENT, "fanout candidates: null argument");
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
+    hipStream_t st = stream ? (hipStream_t)stream : impc_lib::stream(ctx);
     const int64_t total = instances * 6 * (int64_t)(num_obstacles + 1) * pred_len;
-    const int64_t blocks = std::min<int64_t>((total + 255) / 256, (int64_t)ctx->num_cu * 16);
+    const int64_t blocks = std::min<int64_t>((total + 255) / 256, (int64_t)impc_lib::num_cu(ctx) * 16);
     hipLaunchKernelGGL(impc_fanout::k_fanout_candidates, dim3((unsigned)blocks), dim3(256), 0, st, instances,
                        num_obstacles, pred_len, cand_slot, single_pos, single_size, pair_pos, pair_size, x_single,
                        n_single, x_pair, n_pair, x_cand, dyn_count, dyn_pos, dyn_size);
@@ -208,16 +216,16 @@ extern "C" int impc_intent_fanout_device(impc_ctx ctx, int64_t instances, int32_
                                          int32_t *ob_idx, int32_t *cand_type, int32_t *cand_slot,
                                          double *closest_prob, double *single_pos, double *single_size,
                                          double *pair_pos, double *pair_size, void *stream) {
-    if (!ctx) return fail(IMPC_INVALID_ARGUMENT, "null context");
+    if (!ctx) return set_error(IMPC_INVALID_ARGUMENT, "null context");
     if (instances < 0 || num_obstacles < 1 || pred_len < 1 || prev_len < 0)
-        return fail(IMPC_INVALID_ARGUMENT, "fanout: need instances >= 0, K >= 1, L >= 1, P >= 0");
+        return set_error(IMPC_INVALID_ARGUMENT, "fanout: need instances >= 0, K >= 1, L >= 1, P >= 0");
     if (instances == 0) return IMPC_OK;
     if (!curr_pos || !first_time || !prev_count || (prev_len > 0 && !prev_states) || !dyn_cur || !pred_pos ||
         !pred_size || !prob || !ob_idx || !cand_type || !cand_slot || !closest_prob || !single_pos || !single_size ||
         !pair_pos || !pair_size)
-        return fail(IMPC_INVALID_ARGUMENT, "fanout: null argument");
-    HIP_OK(hipSetDevice(ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+        return set_error(IMPC_INVALID_ARGUMENT, "fanout: null argument");
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
+    hipStream_t st = stream ? (hipStream_t)stream : impc_lib::stream(ctx);
     // (no scratch: the other obstacles' most probable intents are recomputed where they are used;
     // a stream-ordered hipMallocAsync scratch for them was read back as zeros on some calls)
     impc_fanout::Args a{instances, num_obstacles, pred_len, prev_len, curr_pos, first_time, prev_states,
@@ -226,7 +234,7 @@ extern "C" int impc_intent_fanout_device(impc_ctx ctx, int64_t instances, int32_
     hipLaunchKernelGGL(impc_fanout::k_fanout_pick, dim3((unsigned)((instances + 63) / 64)), dim3(64), 0, st, a);
     HIP_OK(hipGetLastError());
     const int64_t rows = instances * (4LL * num_obstacles + 2LL * (num_obstacles + 1)) * pred_len;
-    const int64_t blocks = std::min<int64_t>((rows + 255) / 256, (int64_t)ctx->num_cu * 16);
+    const int64_t blocks = std::min<int64_t>((rows + 255) / 256, (int64_t)impc_lib::num_cu(ctx) * 16);
     hipLaunchKernelGGL(impc_fanout::k_fanout_copy, dim3((unsigned)blocks), dim3(256), 0, st, a);
     HIP_OK(hipGetLastError());
     return IMPC_OK;
@@ -238,9 +246,9 @@ extern "C" int impc_intent_fanout(impc_ctx ctx, int64_t instances, int32_t num_o
                                   const double *pred_pos, const double *pred_size, const double *prob,
                                   int32_t *ob_idx, int32_t *cand_type, int32_t *cand_slot, double *closest_prob,
                                   double *single_pos, double *single_size, double *pair_pos, double *pair_size) {
-    if (!ctx) return fail(IMPC_INVALID_ARGUMENT, "null context");
+    if (!ctx) return set_error(IMPC_INVALID_ARGUMENT, "null context");
     if (instances < 0 || num_obstacles < 1 || pred_len < 1 || prev_len < 0)
-        return fail(IMPC_INVALID_ARGUMENT, "fanout: need instances >= 0, K >= 1, L >= 1, P >= 0");
+        return set_error(IMPC_INVALID_ARGUMENT, "fanout: need instances >= 0, K >= 1, L >= 1, P >= 0");
     if (instances == 0) return IMPC_OK;
     const size_t I = (size_t)instances, K = (size_t)num_obstacles, L = (size_t)pred_len, P = (size_t)prev_len;
     const size_t parts[] = {8 * I * 3,     I,         8 * I * P * 8,     4 * I,         8 * I * K * 3,
@@ -253,10 +261,10 @@ extern "C" int impc_intent_fanout(impc_ctx ctx, int64_t instances, int32_t num_o
         off[k] = total;
         total += (parts[k] + 255) & ~(size_t)255;
     }
-    HIP_OK(hipSetDevice(ctx->device));
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
     char *buf = nullptr;
     HIP_OK(hipMalloc((void **)&buf, total));
-    hipStream_t st = ctx->stream;
+    hipStream_t st = impc_lib::stream(ctx);
     const void *srcs[NIN] = {curr_pos, first_time, prev_states, prev_count, dyn_cur, pred_pos, pred_size, prob};
     void *dsts[NP - NIN] = {ob_idx, cand_type, cand_slot, closest_prob, single_pos, single_size, pair_pos, pair_size};
     hipError_t e = hipSuccess;
@@ -264,7 +272,7 @@ extern "C" int impc_intent_fanout(impc_ctx ctx, int64_t instances, int32_t num_o
         if (parts[k] && srcs[k]) e = hipMemcpyAsync(buf + off[k], srcs[k], parts[k], hipMemcpyHostToDevice, st);
     int rc = IMPC_OK;
     if (e != hipSuccess) {
-        rc = fail(IMPC_DEVICE_ERROR, std::string("fanout upload: ") + hipGetErrorString(e));
+        rc = set_error(IMPC_DEVICE_ERROR, std::string("fanout upload: ") + hipGetErrorString(e));
     } else {
         auto D = [&](int k) { return (void *)(buf + off[k]); };
         rc = impc_intent_fanout_device(ctx, instances, num_obstacles, pred_len, prev_len, (const double *)D(0),
@@ -278,7 +286,7 @@ extern "C" int impc_intent_fanout(impc_ctx ctx, int64_t instances, int32_t num_o
         for (int k = NIN; k < NP && e == hipSuccess; k++)
             e = hipMemcpyAsync(dsts[k - NIN], buf + off[k], parts[k], hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(IMPC_DEVICE_ERROR, std::string("fanout download: ") + hipGetErrorString(e));
+        if (e != hipSuccess) rc = set_error(IMPC_DEVICE_ERROR, std::string("fanout download: ") + hipGetErrorString(e));
     } else {
         (void)hipStreamSynchronize(st);
     }

@@ -22,28 +22,21 @@
 #include <vector>
 
 #include "../../include/impc_qp.h"
-#include "../../include/impc_select.h"
 #include "../../include/impc_mpc.h"
-#include "../../include/impc_fanout.h"
-#include "../../include/impc_predict.h"
-#include "../../include/impc_detect.h"
 #include "../../include/impc_comm.h"
 #include "../../include/impc_replan.h"
 #include "lib_internal.hpp"
-#include "mpc_qp_internal.hpp"
 #include "admm_core.hpp"
 #include "mpc_structure.hpp"
 #include "mpc_wave.hpp"
 #include "queue.hpp"
 #include "symbolic.hpp"
 
-#ifndef IMPC_BUILD_ID  // set by the Makefile: hash of the compiled sources and flags
-#define IMPC_BUILD_ID "src-unknown"
-#endif
-#ifndef IMPC_GIT_REV
-#define IMPC_GIT_REV "unknown"
-#endif
-#define IMPC_VERSION "impc_qp 0.3.0 (OSQP 0.6.2 semantics, gfx950, git " IMPC_GIT_REV ")"
+using impc_lib::ctx_note_launch;
+using impc_lib::ctx_order_after_all;
+using impc_lib::ctx_order_launch;
+using impc_lib::ctx_quiesce;
+using impc_lib::h2d_sync;
 
 namespace {
 
@@ -53,13 +46,6 @@ int fail(int code, const std::string &msg) {
     g_last_error = msg;
     return code;
 }
-
-#define HIP_OK(expr)                                                                             \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return fail(IMPC_DEVICE_ERROR, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 constexpr int kBlock = 64;  // generic path: one wavefront per workgroup, one QP per lane
 constexpr int kTile = 64;   // transpose tile edge
@@ -560,7 +546,7 @@ struct impc_ctx_s {
 // when the call returns: the solver's kernels run on that stream, which is non-blocking, so the
 // legacy null stream of a plain hipMemcpy / hipMemset would not be ordered before them (a pageable
 // hipMemcpy may also return before its DMA lands).
-static int h2d_sync(hipStream_t st, void *dst, const void *src, size_t bytes) {
+int impc_lib::h2d_sync(hipStream_t st, void *dst, const void *src, size_t bytes) {
     if (!bytes) return IMPC_OK;
     HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
     HIP_OK(hipStreamSynchronize(st));
@@ -572,11 +558,6 @@ static int fill0_sync(hipStream_t st, void *dst, size_t bytes) {
     HIP_OK(hipStreamSynchronize(st));
     return IMPC_OK;
 }
-#define IMPC_TRY(expr)          \
-    do {                        \
-        int rc_ = (expr);       \
-        if (rc_) return rc_;    \
-    } while (0)
 
 // Caller streams (impc_batch_setup / _solve / _solve_group accept one) are ordered against the
 // context's own stream in both directions: a launch on a caller stream first waits for what is
@@ -584,7 +565,7 @@ static int fill0_sync(hipStream_t st, void *dst, size_t bytes) {
 // starts), and every entry point that rewrites batch inputs, workspaces or the group-entry table
 // first waits for every launch issued on a caller stream (an event recorded after each one), so
 // no kernel in flight on another stream reads half-replaced data.
-static int ctx_order_launch(impc_ctx ctx, hipStream_t st) {
+int impc_lib::ctx_order_launch(impc_ctx ctx, hipStream_t st) {
     if (st == ctx->stream) return IMPC_OK;
     if (!ctx->ev_order) HIP_OK(hipEventCreateWithFlags(&ctx->ev_order, hipEventDisableTiming));
     HIP_OK(hipEventRecord(ctx->ev_order, ctx->stream));
@@ -594,12 +575,12 @@ static int ctx_order_launch(impc_ctx ctx, hipStream_t st) {
 // st waits for every launch noted on any caller stream (ctx_note_launch) as well as for the
 // context stream: for consumers of results that may have been produced on another stream (the
 // cost gather) and of scratch an earlier call on another stream may still be reading
-static int ctx_order_after_all(impc_ctx ctx, hipStream_t st) {
+int impc_lib::ctx_order_after_all(impc_ctx ctx, hipStream_t st) {
     if (st != ctx->stream) IMPC_TRY(ctx_order_launch(ctx, st));
     for (hipEvent_t e : ctx->ev_pending) HIP_OK(hipStreamWaitEvent(st, e, 0));
     return IMPC_OK;
 }
-static int ctx_note_launch(impc_ctx ctx, hipStream_t st) {
+int impc_lib::ctx_note_launch(impc_ctx ctx, hipStream_t st) {
     if (st == ctx->stream) return IMPC_OK;
     // recycle the events of launches that have completed (keeps the pending list short)
     for (size_t k = 0; k < ctx->ev_pending.size();) {
@@ -622,7 +603,7 @@ static int ctx_note_launch(impc_ctx ctx, hipStream_t st) {
     ctx->ev_pending.push_back(e);
     return IMPC_OK;
 }
-static int ctx_quiesce(impc_ctx ctx) {
+int impc_lib::ctx_quiesce(impc_ctx ctx) {
     HIP_OK(hipStreamSynchronize(ctx->stream));
     for (hipEvent_t e : ctx->ev_pending) HIP_OK(hipEventSynchronize(e));
     ctx->ev_pool.insert(ctx->ev_pool.end(), ctx->ev_pending.begin(), ctx->ev_pending.end());
@@ -1430,8 +1411,6 @@ void impc_default_settings(impc_settings *s) {
 }
 
 const char *impc_last_error(void) { return g_last_error.c_str(); }
-const char *impc_version(void) { return IMPC_VERSION; }
-const char *impc_build_id(void) { return IMPC_BUILD_ID; }
 
 int impc_ctx_create(int device, impc_ctx *out) {
     if (!out) return fail(IMPC_INVALID_ARGUMENT, "null output pointer");
@@ -1488,6 +1467,36 @@ int impc_ctx_synchronize(impc_ctx ctx) {
     HIP_OK(hipStreamSynchronize(ctx->stream));
     HIP_OK(hipDeviceSynchronize());
     return IMPC_OK;
+}
+
+int impc_ctx_timer_mark(impc_ctx ctx, void *stream) {
+    if (!ctx) return fail(IMPC_INVALID_ARGUMENT, "null context");
+    HIP_OK(hipSetDevice(ctx->device));
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    hipEvent_t e = nullptr;
+    HIP_OK(hipEventCreate(&e));
+    ctx->timer_marks.push_back(e);
+    HIP_OK(hipEventRecord(e, st));
+    return IMPC_OK;
+}
+
+int impc_ctx_timer_read(impc_ctx ctx, double *ms, int64_t max_pairs, int64_t *pairs) {
+    if (!ctx || !pairs || (max_pairs > 0 && !ms)) return fail(IMPC_INVALID_ARGUMENT, "invalid argument");
+    HIP_OK(hipSetDevice(ctx->device));
+    const int64_t np = (int64_t)ctx->timer_marks.size() / 2;
+    int rc = IMPC_OK;
+    for (int64_t k = 0; k < np && k < max_pairs && rc == IMPC_OK; k++) {
+        float t = 0.f;
+        hipEvent_t a = ctx->timer_marks[(size_t)(2 * k)], b = ctx->timer_marks[(size_t)(2 * k + 1)];
+        hipError_t e = hipEventSynchronize(b);
+        if (e == hipSuccess) e = hipEventElapsedTime(&t, a, b);
+        if (e != hipSuccess) rc = fail(IMPC_DEVICE_ERROR, std::string("timer: ") + hipGetErrorString(e));
+        ms[k] = (double)t;
+    }
+    for (hipEvent_t e : ctx->timer_marks) (void)hipEventDestroy(e);
+    ctx->timer_marks.clear();
+    *pairs = std::min(np, max_pairs);
+    return rc;
 }
 
 int impc_batch_create(impc_ctx ctx, int64_t n, int64_t m, const int64_t *Pp, const int64_t *Pi, const int64_t *Ap,
@@ -2595,45 +2604,62 @@ int impc_copy_to_host(impc_ctx ctx, void *dst, const void *src, int64_t bytes) {
     return IMPC_OK;
 }
 
-// ---------------------------------------------------------------- candidate scoring / selection
-#include "select.hpp"
+// ---- a receding window's next initial state from the last solve (impc_batch_follow_plan_device)
+namespace impc_replan_k {
+// mpcPlanner::getPos / getVel (mpcPlanner.cpp:1257-1290) on QP b's own solution, for the QPs
+// whose solve returned one; pos / vel [B][3] updated in place.  Deliberately narrower than
+// solveTraj's success (impc_lib::solve_traj_ok, which the replan's commit uses): a receding window
+// of raw QPs does not move its x0 to an OSQP_NAN plan (infeasible / diverged QPs), DESIGN.md 2
+__global__ void k_follow(int64_t B, int32_t N, int64_t n, double ts, double t, const double *__restrict__ x,
+                         const impc_info *__restrict__ info, double *__restrict__ pos, double *__restrict__ vel,
+                         double *__restrict__ lin) {
+    for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < B; b += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t st = info[b].status_val;
+        if (st != IMPC_SOLVED && st != IMPC_SOLVED_INACCURATE && st != IMPC_MAX_ITER_REACHED &&
+            st != IMPC_TIME_LIMIT_REACHED)
+            continue;
+        int idx = (int)floor(t / ts);
+        const double dt = t - idx * ts;
+        idx = max(0, min(idx, N - 1));
+        const int nxt = min(idx + 1, N - 1);
+        const double *s = x + b * n + 8 * idx, *e = x + b * n + 8 * nxt;
+        for (int c = 0; c < 3; c++) {
+            pos[3 * b + c] = s[c] + (e[c] - s[c]) / ts * dt;
+            vel[3 * b + c] = s[3 + c] + (e[3 + c] - s[3 + c]) / ts * dt;
+        }
+        // currentStatesSol_: the next linearisation point (castMPCToQPConstraintMatrix :1042-1051)
+        if (lin)
+            for (int k = 0; k < 8 * N; k++) lin[b * 8 * (int64_t)N + k] = x[b * n + k];
+    }
+}
+}  // namespace impc_replan_k
 
-// ---------------------------------------------------------------- intent-hypothesis fan-out
-#include "fanout.hpp"
+extern "C" int impc_batch_follow_plan_device(impc_batch b, int32_t horizon, double ts, double t, double *pos,
+                                             double *vel, double *lin_states) {
+    if (!b || horizon < 2 || b->n != 13 * (int64_t)horizon - 5 || !(ts > 0.0) || !(t >= 0.0) || !pos || !vel)
+        return fail(IMPC_INVALID_ARGUMENT, "follow plan: an mpcPlanner batch (n = 13 horizon - 5), ts > 0, t >= 0");
+    HIP_OK(hipSetDevice(b->ctx->device));
+    hipStream_t st = b->ctx->stream;
+    IMPC_TRY(ctx_order_after_all(b->ctx, st));  // after the solve, wherever it ran
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((b->Bact + 255) / 256, 4096));
+    hipLaunchKernelGGL(impc_replan_k::k_follow, dim3(blocks), dim3(256), 0, st, b->Bact, horizon, b->n, ts, t, b->d_xout,
+                       b->d_info, pos, vel, lin_states);
+    HIP_OK(hipGetLastError());
+    return IMPC_OK;
+}
 
-// ---------------------------------------------------------------- obstacle intent probabilities
-#include "predict.hpp"
-
-// ---------------------------------------------------------------- detector track store, range gate
-#include "detect.hpp"
-
-// ---------------------------------------------------------------- on-device MPC -> QP assembly
-#include "mpc_build.hpp"
-
-// ---------------------------------------------------------------- RCCL communicator, step timer
-#include "comm.hpp"
-
-// ---------------------------------------------------------------- reference trajectory (getXRef)
-#include "reftraj.hpp"
-
-// ---------------------------------------------------------------- replan state (impc_replan.h)
-#include "replan.hpp"
-
-// ---------------------------------------------------------------- hooks for the library's other
-// translation units (lib_internal.hpp; replan_run.hip): error reporting, stream ordering, and
-// direct writes into a batch's device input arrays
+// ---------------------------------------------------------------- the rest of lib_internal.hpp for
+// the library's other translation units: error reporting, the context's fields, and direct writes
+// into a batch's device input arrays
 namespace impc_lib {
 int set_error(int code, const std::string &msg) { return fail(code, msg); }
 int num_cu(impc_ctx ctx) { return ctx->num_cu; }
 int device(impc_ctx ctx) { return ctx->device; }
 hipStream_t stream(impc_ctx ctx) { return ctx->stream; }
-int order_after_all(impc_ctx ctx) {
-    HIP_OK(hipSetDevice(ctx->device));
-    return ctx_order_after_all(ctx, ctx->stream);
-}
 int batch_inputs_begin(impc_batch b, BatchInputs *out) {
     if (!b || !out) return fail(IMPC_INVALID_ARGUMENT, "null batch");
-    IMPC_TRY(order_after_all(b->ctx));  // no launch on any stream still reads the arrays handed out
+    HIP_OK(hipSetDevice(b->ctx->device));
+    IMPC_TRY(ctx_order_after_all(b->ctx, b->ctx->stream));  // no launch anywhere still reads the arrays handed out
     b->in_dirty = b->ws_dirty = false;   // staged host copies are superseded
     out->Px = b->in_Px, out->q = b->in_q, out->Ax = b->in_Ax, out->l = b->in_l, out->u = b->in_u;
     out->xws = b->in_xws;
@@ -2645,6 +2671,11 @@ int batch_inputs_view(impc_batch b, BatchInputs *out) {
     out->Px = b->in_Px, out->q = b->in_q, out->Ax = b->in_Ax, out->l = b->in_l, out->u = b->in_u;
     out->xws = b->in_xws;
     out->n = b->n, out->m = b->m, out->nnzP = b->nnzP, out->nnzA = b->nnzA, out->B = b->B;
+    return IMPC_OK;
+}
+int batch_info_view(impc_batch b, impc_ctx *ctx, int64_t *B, const impc_info **info) {
+    if (!b || !ctx || !B || !info) return fail(IMPC_INVALID_ARGUMENT, "null batch");
+    *ctx = b->ctx, *B = b->B, *info = b->d_info;
     return IMPC_OK;
 }
 int batch_set_active_device(impc_batch b, const int64_t *d_count) {
@@ -2670,41 +2701,6 @@ int batch_tlim_device(impc_batch b, double **out) {
     return IMPC_OK;
 }
 double tick_s(impc_ctx ctx) { return ctx->tick_s; }
-int comm_view(impc_comm c, impc_ctx *ctx, int *rank, int *world) {
-    if (!c || !ctx || !rank || !world) return fail(IMPC_INVALID_ARGUMENT, "null communicator");
-    *ctx = c->ctx, *rank = c->rank, *world = c->world;
-    return IMPC_OK;
-}
-int build_rows(impc_mpc_builder bd, int64_t cap, const int64_t *dcount, const int32_t *row_inst, const int64_t *osrc,
-               const double *pos, const double *vel, const double *xref, const double *lin, const double *pred_pos,
-               const double *pred_size, const double *held_pos, const double *held_size, const double *st_centroid,
-               const double *st_size, const double *st_yaw, int32_t st_stride, const BatchInputs &out, hipStream_t st) {
-    if (!bd || cap < 1) return fail(IMPC_INVALID_ARGUMENT, "build_rows: null builder or empty capacity");
-    if (bd->S > 0 && (!st_centroid || !st_size || !st_yaw))
-        return fail(IMPC_INVALID_ARGUMENT, "build_rows: static obstacles required by the builder");
-    if (bd->S > 0 && st_stride < bd->S)
-        return fail(IMPC_INVALID_ARGUMENT, "build_rows: the static arrays' stride is below the builder's count");
-    impc_build::Args a{cap, bd->n, bd->m, bd->nnzP, bd->nnzA, bd->obs_off, bd->N, bd->W, bd->S, bd->Kd, bd->K, bd->L,
-                       bd->p.dynamic_safety_dist, bd->p.static_safety_dist, bd->p.position_weight,
-                       bd->p.velocity_weight, bd->d_tPx, bd->d_tAx, bd->d_tl, bd->d_tu, bd->d_slot, pos, vel, xref,
-                       lin, st_centroid, st_size, st_yaw, pred_pos, pred_size, out.Px, out.q, out.Ax, out.l, out.u};
-    a.dcount = dcount, a.row_inst = row_inst, a.osrc = osrc, a.hp = held_pos, a.hs = held_size;
-    a.Sst = st_stride;
-    const int64_t groups = std::min<int64_t>(cap, (int64_t)bd->ctx->num_cu * 8);
-    hipLaunchKernelGGL(impc_build::k_build, dim3((unsigned)groups), dim3(256), 0, st, a);
-    HIP_OK(hipGetLastError());
-    return IMPC_OK;
-}
-int select_best_counted(impc_ctx ctx, const impc_select_params *p, int64_t instances, const double *const *x_cand,
-                        const int8_t *valid, const int8_t *first_time, const double *prev_states,
-                        const int32_t *prev_count, const double *xref, const double *st_centroid,
-                        const double *st_size, const int32_t *st_count, const int32_t *dyn_count, const double *dyn_pos,
-                        const double *dyn_size, const double *prob, int32_t *best_cand, int32_t *best_pos,
-                        double *scores, double *weighted, void *stream) {
-    return impc_select::launch(ctx, p, instances, x_cand, valid, first_time, prev_states, prev_count, xref, st_centroid,
-                               st_size, st_count, dyn_count, dyn_pos, dyn_size, prob, best_cand, best_pos, scores,
-                               weighted, stream);
-}
 int batch_inputs_end(impc_batch b, bool warm_x) {
     if (!b) return fail(IMPC_INVALID_ARGUMENT, "null batch");
     b->shared = false;

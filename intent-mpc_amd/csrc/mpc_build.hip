@@ -1,9 +1,19 @@
-// mpc_build.hpp -- on-device MPC -> QP assembly (include/impc_mpc.h, impc_mpc_build_values_device),
-// included by impc_qp.hip.  Restates the instance-dependent part of mpcPlanner's
+// mpc_build.hip -- on-device MPC -> QP assembly (include/impc_mpc.h, impc_mpc_build_values_device),
+// its own translation unit of libimpc_qp.so.  Restates the instance-dependent part of mpcPlanner's
 // castMPCToQPGradient (:952-966), castMPCToQPConstraintMatrix obstacle rows (:1040-1071),
 // castMPCToQPConstraintVectors (:1074-1146) and updateObstacleParam (:1148-1197); everything
 // else is copied from templates the host builder produced for the shape.
-#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <memory>
+#include <vector>
+
+#include "../../include/impc_mpc.h"
+#include "lib_internal.hpp"
+#include "mpc_qp_internal.hpp"
+
+using impc_lib::set_error;
 
 struct impc_mpc_builder_s {
     impc_ctx ctx = nullptr;
@@ -130,11 +140,11 @@ __global__ __launch_bounds__(256) void k_build(Args a) {
 
 extern "C" int impc_mpc_builder_create(impc_ctx ctx, const impc_mpc_params *p, int32_t num_static, int32_t num_dynamic,
                                        int32_t pred_len, impc_mpc_builder *out) {
-    if (!ctx || !p || !out) return fail(IMPC_INVALID_ARGUMENT, "null argument");
+    if (!ctx || !p || !out) return set_error(IMPC_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
-    if (num_dynamic > 0 && pred_len < 1) return fail(IMPC_INVALID_ARGUMENT, "pred_len must be >= 1");
+    if (num_dynamic > 0 && pred_len < 1) return set_error(IMPC_INVALID_ARGUMENT, "pred_len must be >= 1");
     impc_qp_dims dm;
-    if (impc_mpc_dims(p, num_static, num_dynamic, &dm)) return fail(IMPC_INVALID_ARGUMENT, "invalid MPC shape");
+    if (impc_mpc_dims(p, num_static, num_dynamic, &dm)) return set_error(IMPC_INVALID_ARGUMENT, "invalid MPC shape");
     std::unique_ptr<impc_mpc_builder_s> b(new impc_mpc_builder_s());
     b->ctx = ctx;
     b->p = *p;
@@ -143,7 +153,7 @@ extern "C" int impc_mpc_builder_create(impc_ctx ctx, const impc_mpc_params *p, i
     b->n = dm.n, b->m = dm.m, b->nnzP = dm.nnzP, b->nnzA = dm.nnzA;
     std::vector<int64_t> slots;
     if (impc_mpc_obstacle_layout(p, num_static, num_dynamic, slots, b->obs_off))
-        return fail(IMPC_INVALID_ARGUMENT, "invalid MPC shape");
+        return set_error(IMPC_INVALID_ARGUMENT, "invalid MPC shape");
     // templates: the host builder on one neutral instance (its instance-dependent entries are
     // overwritten by the kernel)
     const int N = b->N, S = b->S, Kd = b->Kd, L = b->L;
@@ -152,26 +162,48 @@ extern "C" int impc_mpc_builder_create(impc_ctx ctx, const impc_mpc_params *p, i
     std::vector<double> Px((size_t)b->nnzP), q((size_t)b->n), Ax((size_t)b->nnzA), l((size_t)b->m), u((size_t)b->m);
     if (impc_mpc_build_values(p, 1, z3.data(), z3.data(), xr.data(), nullptr, S, sc.data(), ss.data(), sy.data(),
                               Kd, L, dp.data(), ds.data(), Px.data(), q.data(), Ax.data(), l.data(), u.data()))
-        return fail(IMPC_INVALID_ARGUMENT, "host builder rejected the shape");
+        return set_error(IMPC_INVALID_ARGUMENT, "host builder rejected the shape");
     std::vector<int32_t> sl32(slots.begin(), slots.end());
-    HIP_OK(hipSetDevice(ctx->device));
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
     HIP_OK(hipMalloc((void **)&b->d_tPx, sizeof(double) * std::max<int64_t>(1, b->nnzP)));
     HIP_OK(hipMalloc((void **)&b->d_tAx, sizeof(double) * b->nnzA));
     HIP_OK(hipMalloc((void **)&b->d_tl, sizeof(double) * b->m));
     HIP_OK(hipMalloc((void **)&b->d_tu, sizeof(double) * b->m));
     HIP_OK(hipMalloc((void **)&b->d_slot, sizeof(int32_t) * std::max<size_t>(1, sl32.size())));
-    IMPC_TRY(h2d_sync(ctx->stream, b->d_tPx, Px.data(), sizeof(double) * b->nnzP));
-    IMPC_TRY(h2d_sync(ctx->stream, b->d_tAx, Ax.data(), sizeof(double) * b->nnzA));
-    IMPC_TRY(h2d_sync(ctx->stream, b->d_tl, l.data(), sizeof(double) * b->m));
-    IMPC_TRY(h2d_sync(ctx->stream, b->d_tu, u.data(), sizeof(double) * b->m));
-    IMPC_TRY(h2d_sync(ctx->stream, b->d_slot, sl32.data(), sizeof(int32_t) * sl32.size()));
+    IMPC_TRY(impc_lib::h2d_sync(impc_lib::stream(ctx), b->d_tPx, Px.data(), sizeof(double) * b->nnzP));
+    IMPC_TRY(impc_lib::h2d_sync(impc_lib::stream(ctx), b->d_tAx, Ax.data(), sizeof(double) * b->nnzA));
+    IMPC_TRY(impc_lib::h2d_sync(impc_lib::stream(ctx), b->d_tl, l.data(), sizeof(double) * b->m));
+    IMPC_TRY(impc_lib::h2d_sync(impc_lib::stream(ctx), b->d_tu, u.data(), sizeof(double) * b->m));
+    IMPC_TRY(impc_lib::h2d_sync(impc_lib::stream(ctx), b->d_slot, sl32.data(), sizeof(int32_t) * sl32.size()));
     *out = b.release();
+    return IMPC_OK;
+}
+
+int impc_lib::build_rows(impc_mpc_builder bd, int64_t cap, const int64_t *dcount, const int32_t *row_inst,
+                         const int64_t *osrc, const double *pos, const double *vel, const double *xref,
+                         const double *lin, const double *pred_pos, const double *pred_size, const double *held_pos,
+                         const double *held_size, const double *st_centroid, const double *st_size,
+                         const double *st_yaw, int32_t st_stride, const BatchInputs &out, hipStream_t st) {
+    if (!bd || cap < 1) return set_error(IMPC_INVALID_ARGUMENT, "build_rows: null builder or empty capacity");
+    if (bd->S > 0 && (!st_centroid || !st_size || !st_yaw))
+        return set_error(IMPC_INVALID_ARGUMENT, "build_rows: static obstacles required by the builder");
+    if (bd->S > 0 && st_stride < bd->S)
+        return set_error(IMPC_INVALID_ARGUMENT, "build_rows: the static arrays' stride is below the builder's count");
+    impc_build::Args a{cap, bd->n, bd->m, bd->nnzP, bd->nnzA, bd->obs_off, bd->N, bd->W, bd->S, bd->Kd, bd->K, bd->L,
+                       bd->p.dynamic_safety_dist, bd->p.static_safety_dist, bd->p.position_weight,
+                       bd->p.velocity_weight, bd->d_tPx, bd->d_tAx, bd->d_tl, bd->d_tu, bd->d_slot, pos, vel, xref,
+                       lin, st_centroid, st_size, st_yaw, pred_pos, pred_size, out.Px, out.q, out.Ax, out.l, out.u};
+    a.dcount = dcount, a.row_inst = row_inst, a.osrc = osrc, a.hp = held_pos, a.hs = held_size;
+    a.Sst = st_stride;
+    const int64_t groups = std::min<int64_t>(cap, (int64_t)impc_lib::num_cu(bd->ctx) * 8);
+    hipLaunchKernelGGL(impc_build::k_build, dim3((unsigned)groups), dim3(256), 0, st, a);
+    HIP_OK(hipGetLastError());
     return IMPC_OK;
 }
 
 extern "C" int impc_mpc_builder_destroy(impc_mpc_builder b) {
     if (!b) return IMPC_OK;
-    if (b->ctx) (void)hipSetDevice(b->ctx->device);
+    if (b->ctx) (void)hipSetDevice(impc_lib::device(b->ctx));
     void *ptrs[] = {b->d_tPx, b->d_tAx, b->d_tl, b->d_tu, b->d_slot};
     for (void *ptr : ptrs)
         if (ptr) (void)hipFree(ptr);
@@ -184,20 +216,20 @@ extern "C" int impc_mpc_build_values_device(impc_mpc_builder b, int64_t nb, cons
                                             const double *st_centroid, const double *st_size, const double *st_yaw,
                                             const double *dyn_pos, const double *dyn_size, double *Px, double *q,
                                             double *Ax, double *l, double *u, void *stream) {
-    if (!b) return fail(IMPC_INVALID_ARGUMENT, "null builder");
-    if (nb < 0) return fail(IMPC_INVALID_ARGUMENT, "negative batch");
+    if (!b) return set_error(IMPC_INVALID_ARGUMENT, "null builder");
+    if (nb < 0) return set_error(IMPC_INVALID_ARGUMENT, "negative batch");
     if (nb == 0) return IMPC_OK;
     if (!curr_pos || !curr_vel || !xref || !Px || !q || !Ax || !l || !u || (b->S > 0 && (!st_centroid || !st_size || !st_yaw)) ||
         (b->Kd > 0 && (!dyn_pos || !dyn_size)))
-        return fail(IMPC_INVALID_ARGUMENT, "null argument");
-    HIP_OK(hipSetDevice(b->ctx->device));
+        return set_error(IMPC_INVALID_ARGUMENT, "null argument");
+    HIP_OK(hipSetDevice(impc_lib::device(b->ctx)));
     impc_build::Args a{nb, b->n, b->m, b->nnzP, b->nnzA, b->obs_off, b->N, b->W, b->S, b->Kd, b->K, b->L,
                        b->p.dynamic_safety_dist, b->p.static_safety_dist, b->p.position_weight, b->p.velocity_weight,
                        b->d_tPx, b->d_tAx, b->d_tl, b->d_tu, b->d_slot, curr_pos, curr_vel, xref, lin_states,
                        st_centroid, st_size, st_yaw, dyn_pos, dyn_size, Px, q, Ax, l, u};
     a.Sst = b->S;
-    hipStream_t st = stream ? (hipStream_t)stream : b->ctx->stream;
-    const int64_t groups = std::min<int64_t>(nb, (int64_t)b->ctx->num_cu * 8);
+    hipStream_t st = stream ? (hipStream_t)stream : impc_lib::stream(b->ctx);
+    const int64_t groups = std::min<int64_t>(nb, (int64_t)impc_lib::num_cu(b->ctx) * 8);
     hipLaunchKernelGGL(impc_build::k_build, dim3((unsigned)groups), dim3(256), 0, st, a);
     HIP_OK(hipGetLastError());
     return IMPC_OK;

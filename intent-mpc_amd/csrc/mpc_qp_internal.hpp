@@ -1,4 +1,4 @@
-// mpc_qp_internal.hpp -- host builder facts used by the device builder (impc_qp.hip), not ABI.
+// mpc_qp_internal.hpp -- host builder facts used by the device builder (mpc_build.hip), not ABI.
 #pragma once
 #include <cstdint>
 #include <vector>

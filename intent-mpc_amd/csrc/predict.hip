@@ -1,8 +1,16 @@
-// predict.hpp -- intent probabilities of tracked obstacles (include/impc_predict.h), included by
-// impc_qp.hip.  One thread per obstacle walks its history (a 4-state Markov chain with a 4 x 4
+// predict.hip -- intent probabilities of tracked obstacles (include/impc_predict.h), its own
+// translation unit of libimpc_qp.so.  One thread per obstacle walks its history (a 4-state Markov chain with a 4 x 4
 // transition matrix per step, dynamicPredictor.cpp:197-281); the work is a few hundred flops per
 // history step, so the kernel is latency-bound and tiny next to the solve.
-#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <string>
+
+#include "../../include/impc_predict.h"
+#include "lib_internal.hpp"
+
+using impc_lib::set_error;
 
 namespace impc_predict {
 
@@ -262,15 +270,15 @@ extern "C" int impc_predict_traj_device(impc_ctx ctx, const impc_traj_params *tp
                                         const uint8_t *occ_inflated, int64_t count, const double *pos,
                                         const double *vel, const double *size, double *pred_pos, double *pred_size,
                                         void *stream) {
-    if (!ctx || !tp || !map) return fail(IMPC_INVALID_ARGUMENT, "null argument");
+    if (!ctx || !tp || !map) return set_error(IMPC_INVALID_ARGUMENT, "null argument");
     if (count < 0 || tp->num_pred < 0 || !(map->resolution > 0) || map->dims[0] < 0 || map->dims[1] < 0 ||
         map->dims[2] < 0)
-        return fail(IMPC_INVALID_ARGUMENT, "predict_traj: bad sizes");
+        return set_error(IMPC_INVALID_ARGUMENT, "predict_traj: bad sizes");
     if (count == 0) return IMPC_OK;
     if (!occ_inflated || !pos || !vel || !size || !pred_pos || !pred_size)
-        return fail(IMPC_INVALID_ARGUMENT, "predict_traj: null array");
-    HIP_OK(hipSetDevice(ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+        return set_error(IMPC_INVALID_ARGUMENT, "predict_traj: null array");
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
+    hipStream_t st = stream ? (hipStream_t)stream : impc_lib::stream(ctx);
     impc_predict::TrajArgs a{*tp, *map, occ_inflated, count, pos, vel, size, pred_pos, pred_size};
     hipLaunchKernelGGL(impc_predict::k_predict_traj, dim3((unsigned)((4 * count + 63) / 64)), dim3(64), 0, st, a);
     HIP_OK(hipGetLastError());
@@ -280,11 +288,11 @@ extern "C" int impc_predict_traj_device(impc_ctx ctx, const impc_traj_params *tp
 extern "C" int impc_predict_traj(impc_ctx ctx, const impc_traj_params *tp, const impc_occ_map *map,
                                  const uint8_t *occ_inflated, int64_t count, const double *pos, const double *vel,
                                  const double *size, double *pred_pos, double *pred_size) {
-    if (!ctx || !tp || !map) return fail(IMPC_INVALID_ARGUMENT, "null argument");
+    if (!ctx || !tp || !map) return set_error(IMPC_INVALID_ARGUMENT, "null argument");
     if (count < 0 || tp->num_pred < 0 || map->dims[0] < 0 || map->dims[1] < 0 || map->dims[2] < 0)
-        return fail(IMPC_INVALID_ARGUMENT, "predict_traj: bad sizes");
+        return set_error(IMPC_INVALID_ARGUMENT, "predict_traj: bad sizes");
     if (count == 0) return IMPC_OK;
-    HIP_OK(hipSetDevice(ctx->device));
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
     const size_t nocc = (size_t)map->dims[0] * map->dims[1] * map->dims[2], n3 = sizeof(double) * count * 3,
                  nout = sizeof(double) * count * 4 * (size_t)(tp->num_pred + 1) * 3;
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -294,17 +302,17 @@ extern "C" int impc_predict_traj(impc_ctx ctx, const impc_traj_params *tp, const
     double *dpos = (double *)(buf + up(nocc)), *dvel = (double *)((char *)dpos + up(n3)),
            *dsz = (double *)((char *)dvel + up(n3)), *dpp = (double *)((char *)dsz + up(n3)),
            *dps = (double *)((char *)dpp + up(nout));
-    hipStream_t st = ctx->stream;
-    int rc = h2d_sync(st, docc, occ_inflated, nocc);
-    if (!rc) rc = h2d_sync(st, dpos, pos, n3);
-    if (!rc) rc = h2d_sync(st, dvel, vel, n3);
-    if (!rc) rc = h2d_sync(st, dsz, size, n3);
+    hipStream_t st = impc_lib::stream(ctx);
+    int rc = impc_lib::h2d_sync(st, docc, occ_inflated, nocc);
+    if (!rc) rc = impc_lib::h2d_sync(st, dpos, pos, n3);
+    if (!rc) rc = impc_lib::h2d_sync(st, dvel, vel, n3);
+    if (!rc) rc = impc_lib::h2d_sync(st, dsz, size, n3);
     if (!rc) rc = impc_predict_traj_device(ctx, tp, map, docc, count, dpos, dvel, dsz, dpp, dps, nullptr);
     if (!rc) {
         hipError_t e = hipMemcpyAsync(pred_pos, dpp, nout, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipMemcpyAsync(pred_size, dps, nout, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(IMPC_DEVICE_ERROR, std::string("predict_traj download: ") + hipGetErrorString(e));
+        if (e != hipSuccess) rc = set_error(IMPC_DEVICE_ERROR, std::string("predict_traj download: ") + hipGetErrorString(e));
     }
     (void)hipFree(buf);
     return rc;
@@ -312,9 +320,9 @@ extern "C" int impc_predict_traj(impc_ctx ctx, const impc_traj_params *tp, const
 
 extern "C" int impc_intent_params_from_config(double max_front_prob, double front_angle_deg, double stop_velocity,
                                               double prob_scale, impc_intent_params *out) {
-    if (!out) return fail(IMPC_INVALID_ARGUMENT, "null output");
+    if (!out) return set_error(IMPC_INVALID_ARGUMENT, "null output");
     if (!(3 * max_front_prob - 1 != 0) || !(stop_velocity > 0))
-        return fail(IMPC_INVALID_ARGUMENT, "max_front_prob must differ from 1/3 and stop velocity be > 0");
+        return set_error(IMPC_INVALID_ARGUMENT, "max_front_prob must differ from 1/3 and stop velocity be > 0");
     out->paraml = out->paramr = (1 - max_front_prob) / (3 * max_front_prob - 1);   // :70-76
     const double fa = front_angle_deg * M_PI / 180;                                // :87
     out->paramf = sqrt(fa * fa / (-2 * log(out->paraml * (1 + sin(fa)) - out->paraml)));  // :88
@@ -326,12 +334,12 @@ extern "C" int impc_intent_params_from_config(double max_front_prob, double fron
 extern "C" int impc_intent_prob_device(impc_ctx ctx, const impc_intent_params *p, int64_t count, int32_t H,
                                        const int32_t *hist_len, const double *pos_hist, const double *vel_hist,
                                        double *prob, void *stream) {
-    if (!ctx || !p) return fail(IMPC_INVALID_ARGUMENT, "null argument");
-    if (count < 0 || H < 0) return fail(IMPC_INVALID_ARGUMENT, "negative size");
+    if (!ctx || !p) return set_error(IMPC_INVALID_ARGUMENT, "null argument");
+    if (count < 0 || H < 0) return set_error(IMPC_INVALID_ARGUMENT, "negative size");
     if (count == 0) return IMPC_OK;
-    if (!hist_len || !prob || (H > 0 && (!pos_hist || !vel_hist))) return fail(IMPC_INVALID_ARGUMENT, "null array");
-    HIP_OK(hipSetDevice(ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    if (!hist_len || !prob || (H > 0 && (!pos_hist || !vel_hist))) return set_error(IMPC_INVALID_ARGUMENT, "null array");
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
+    hipStream_t st = stream ? (hipStream_t)stream : impc_lib::stream(ctx);
     hipLaunchKernelGGL(impc_predict::k_intent_prob, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, st, *p, count,
                        (int)H, hist_len, pos_hist, vel_hist, prob);
     HIP_OK(hipGetLastError());
@@ -341,27 +349,27 @@ extern "C" int impc_intent_prob_device(impc_ctx ctx, const impc_intent_params *p
 extern "C" int impc_intent_prob(impc_ctx ctx, const impc_intent_params *p, int64_t count, int32_t H,
                                 const int32_t *hist_len, const double *pos_hist, const double *vel_hist,
                                 double *prob) {
-    if (!ctx || !p) return fail(IMPC_INVALID_ARGUMENT, "null argument");
-    if (count < 0 || H < 0) return fail(IMPC_INVALID_ARGUMENT, "negative size");
+    if (!ctx || !p) return set_error(IMPC_INVALID_ARGUMENT, "null argument");
+    if (count < 0 || H < 0) return set_error(IMPC_INVALID_ARGUMENT, "negative size");
     if (count == 0) return IMPC_OK;
     for (int64_t o = 0; o < count; o++)
-        if (hist_len[o] < 0 || hist_len[o] > H) return fail(IMPC_INVALID_ARGUMENT, "hist_len outside [0, H]");
-    HIP_OK(hipSetDevice(ctx->device));
+        if (hist_len[o] < 0 || hist_len[o] > H) return set_error(IMPC_INVALID_ARGUMENT, "hist_len outside [0, H]");
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
     const size_t nh = sizeof(int32_t) * count, nv = sizeof(double) * count * (size_t)H * 3, np = sizeof(double) * count * 4;
     char *buf = nullptr;
     HIP_OK(hipMalloc((void **)&buf, nh + 2 * nv + np + 1024));
     int32_t *dh = (int32_t *)buf;
     double *dp = (double *)(buf + ((nh + 255) & ~(size_t)255)), *dv = dp + count * (size_t)H * 3,
            *dpr = dv + count * (size_t)H * 3;
-    hipStream_t st = ctx->stream;
-    int rc = h2d_sync(st, dh, hist_len, nh);
-    if (!rc) rc = h2d_sync(st, dp, pos_hist, nv);
-    if (!rc) rc = h2d_sync(st, dv, vel_hist, nv);
+    hipStream_t st = impc_lib::stream(ctx);
+    int rc = impc_lib::h2d_sync(st, dh, hist_len, nh);
+    if (!rc) rc = impc_lib::h2d_sync(st, dp, pos_hist, nv);
+    if (!rc) rc = impc_lib::h2d_sync(st, dv, vel_hist, nv);
     if (!rc) rc = impc_intent_prob_device(ctx, p, count, H, dh, dp, dv, dpr, nullptr);
     if (!rc) {
         hipError_t e = hipMemcpyAsync(prob, dpr, np, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(IMPC_DEVICE_ERROR, std::string("intent prob download: ") + hipGetErrorString(e));
+        if (e != hipSuccess) rc = set_error(IMPC_DEVICE_ERROR, std::string("intent prob download: ") + hipGetErrorString(e));
     }
     (void)hipFree(buf);
     return rc;

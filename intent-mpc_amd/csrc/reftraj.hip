@@ -1,8 +1,15 @@
-// reftraj.hpp -- mpcPlanner::getReferenceTraj / getXRef on the device (include/impc_mpc.h,
-// impc_reference_traj_device), included by impc_qp.hip.  One thread per planning instance: a
+// reftraj.hip -- mpcPlanner::getReferenceTraj / getXRef on the device (include/impc_mpc.h,
+// impc_reference_traj_device), its own translation unit of libimpc_qp.so.  One thread per planning instance: a
 // nearest-point search over the next 3 s of the instance's path from its last start index, then
 // the horizon's points (padded with the path's last point) as the 8-state reference.
-#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "../../include/impc_mpc.h"
+#include "lib_internal.hpp"
+
+using impc_lib::set_error;
 
 namespace impc_reftraj {
 
@@ -61,16 +68,16 @@ extern "C" int impc_reference_traj_device(impc_ctx ctx, int32_t horizon, double 
                                           int32_t repeat, double *xref, void *stream) {
     if (!ctx || horizon < 1 || !(ts > 0.0) || ni < 0 || repeat < 1 ||
         (ni > 0 && (!path_ptr || !curr_pos || !last_idx || !xref)))
-        return fail(IMPC_INVALID_ARGUMENT, "invalid reference-trajectory arguments");
+        return set_error(IMPC_INVALID_ARGUMENT, "invalid reference-trajectory arguments");
     if (ni == 0) return IMPC_OK;
-    HIP_OK(hipSetDevice(ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    IMPC_TRY(ctx_order_launch(ctx, st));
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
+    hipStream_t st = stream ? (hipStream_t)stream : impc_lib::stream(ctx);
+    IMPC_TRY(impc_lib::ctx_order_launch(ctx, st));
     const unsigned blocks = (unsigned)((ni + 255) / 256);
     hipLaunchKernelGGL(impc_reftraj::k_reference_traj, dim3(blocks), dim3(256), 0, st, horizon, ts, ni, path_ptr, path,
                        curr_pos, last_idx, repeat, xref);
     HIP_OK(hipGetLastError());
-    return ctx_note_launch(ctx, st);
+    return impc_lib::ctx_note_launch(ctx, st);
 }
 
 // ---------------------------------------------------------------- per-candidate row copies
@@ -99,14 +106,14 @@ __global__ void k_gather_rows(const T *__restrict__ src, int64_t words, const in
 extern "C" int impc_gather_rows_device(impc_ctx ctx, const void *src, int64_t row_bytes, const int64_t *idx,
                                        int64_t count, void *dst, void *stream) {
     if (!ctx || count < 0 || row_bytes < 0 || (row_bytes & 3) || (count && row_bytes && (!src || !dst || !idx)))
-        return fail(IMPC_INVALID_ARGUMENT, "invalid row-gather arguments (row_bytes a multiple of 4)");
+        return set_error(IMPC_INVALID_ARGUMENT, "invalid row-gather arguments (row_bytes a multiple of 4)");
     if (!count || !row_bytes) return IMPC_OK;
-    HIP_OK(hipSetDevice(ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    IMPC_TRY(ctx_order_launch(ctx, st));
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
+    hipStream_t st = stream ? (hipStream_t)stream : impc_lib::stream(ctx);
+    IMPC_TRY(impc_lib::ctx_order_launch(ctx, st));
     const bool w8 = (row_bytes & 7) == 0;
     const int64_t words = row_bytes / (w8 ? 8 : 4), n = count * words;
-    const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->num_cu * 8);
+    const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)impc_lib::num_cu(ctx) * 8);
     if (w8)
         hipLaunchKernelGGL(impc_reftraj::k_gather_rows<double>, dim3(blocks), dim3(256), 0, st, (const double *)src,
                            words, idx, count, (double *)dst);
@@ -114,21 +121,21 @@ extern "C" int impc_gather_rows_device(impc_ctx ctx, const void *src, int64_t ro
         hipLaunchKernelGGL(impc_reftraj::k_gather_rows<uint32_t>, dim3(blocks), dim3(256), 0, st,
                            (const uint32_t *)src, words, idx, count, (uint32_t *)dst);
     HIP_OK(hipGetLastError());
-    return ctx_note_launch(ctx, st);
+    return impc_lib::ctx_note_launch(ctx, st);
 }
 
 extern "C" int impc_repeat_rows_device(impc_ctx ctx, const void *src, int64_t rows, int64_t row_bytes, int32_t repeat,
                                        void *dst, void *stream) {
     if (!ctx || rows < 0 || row_bytes < 0 || (row_bytes & 7) || repeat < 1 || (rows && row_bytes && (!src || !dst)))
-        return fail(IMPC_INVALID_ARGUMENT, "invalid row-repeat arguments (row_bytes a multiple of 8)");
+        return set_error(IMPC_INVALID_ARGUMENT, "invalid row-repeat arguments (row_bytes a multiple of 8)");
     if (!rows || !row_bytes) return IMPC_OK;
-    HIP_OK(hipSetDevice(ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    IMPC_TRY(ctx_order_launch(ctx, st));
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
+    hipStream_t st = stream ? (hipStream_t)stream : impc_lib::stream(ctx);
+    IMPC_TRY(impc_lib::ctx_order_launch(ctx, st));
     const int64_t n = rows * (row_bytes / 8) * repeat;
-    const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->num_cu * 8);
+    const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)impc_lib::num_cu(ctx) * 8);
     hipLaunchKernelGGL(impc_reftraj::k_repeat_rows, dim3(blocks), dim3(256), 0, st, (const double *)src, rows,
                        row_bytes / 8, repeat, (double *)dst);
     HIP_OK(hipGetLastError());
-    return ctx_note_launch(ctx, st);
+    return impc_lib::ctx_note_launch(ctx, st);
 }

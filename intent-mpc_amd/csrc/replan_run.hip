@@ -44,18 +44,6 @@
 #include "lib_internal.hpp"
 #include "plan_exec.hpp"
 
-#define RP_HIP(expr)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess)                                                                               \
-            return impc_lib::set_error(IMPC_DEVICE_ERROR, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-#define RP_TRY(expr)         \
-    do {                     \
-        int rc_ = (expr);    \
-        if (rc_) return rc_; \
-    } while (0)
-
 namespace impc_rp {
 
 constexpr int kPlanLanes = 512;
@@ -291,7 +279,7 @@ struct PickArgs {
 
 // findClosestObstacle (:663-708, over the instance's K_i obstacles; a fan-out instance is never on
 // its first plan) and getIntentComb's order (:719-756: std::sort of (weight, index) pairs, taken
-// from the back); single-solve instances get -1.  As impc_intent_fanout_device (fanout.hpp), with
+// from the back); single-solve instances get -1.  As impc_intent_fanout_device (fanout.hip), with
 // the obstacle count per instance.
 __global__ __launch_bounds__(64) void k_pick(PickArgs a) {
 #pragma clang fp contract(off)
@@ -613,7 +601,7 @@ __global__ void k_advance(int64_t I, int32_t N, int64_t n, double ts, double t, 
 struct Arena {
     std::vector<void *> ptrs;
     int alloc(size_t bytes, void **out) {
-        RP_HIP(hipMalloc(out, std::max<size_t>(bytes, 8)));
+        HIP_OK(hipMalloc(out, std::max<size_t>(bytes, 8)));
         ptrs.push_back(*out);
         return IMPC_OK;
     }
@@ -702,31 +690,31 @@ const char *const kNoStatic = "replan: per-instance static counts need num_stati
 // *no_kernel: the pattern is not one the structured kernel takes (the only kernel of the grouped solve)
 int make_shape(impc_replan rp, Shape &s, int32_t k, int32_t nst, int64_t cap, bool *no_kernel) {
     s.k = k, s.nst = nst, s.cap = cap;
-    RP_TRY(impc_mpc_dims(&rp->cfg.mpc, nst, k, &s.dm));
+    IMPC_TRY(impc_mpc_dims(&rp->cfg.mpc, nst, k, &s.dm));
     std::vector<int64_t> Pp(s.dm.n + 1), Pi(std::max<int64_t>(s.dm.nnzP, 1)), Ap(s.dm.n + 1), Ai(s.dm.nnzA);
-    RP_TRY(impc_mpc_build_pattern(&rp->cfg.mpc, nst, k, Pp.data(), Pi.data(), Ap.data(), Ai.data()));
-    RP_TRY(impc_batch_create(rp->ctx, s.dm.n, s.dm.m, Pp.data(), Pi.data(), Ap.data(), Ai.data(), cap, &s.batch));
-    RP_TRY(impc_batch_set_settings(s.batch, &rp->cfg.settings));
+    IMPC_TRY(impc_mpc_build_pattern(&rp->cfg.mpc, nst, k, Pp.data(), Pi.data(), Ap.data(), Ai.data()));
+    IMPC_TRY(impc_batch_create(rp->ctx, s.dm.n, s.dm.m, Pp.data(), Pi.data(), Ap.data(), Ai.data(), cap, &s.batch));
+    IMPC_TRY(impc_batch_set_settings(s.batch, &rp->cfg.settings));
     if (rp->cfg.queue_order == IMPC_QUEUE_LONGEST_FIRST) {
         // impc.scenarios.queue_weight: ||q||_inf / (position weight (N - 1)) weighed 1:10
         const double qw = 1.0 / (10.0 * (rp->N - 1) * rp->cfg.mpc.position_weight);
-        RP_TRY(impc_batch_set_queue_order(s.batch, IMPC_QUEUE_LONGEST_FIRST, qw));
+        IMPC_TRY(impc_batch_set_queue_order(s.batch, IMPC_QUEUE_LONGEST_FIRST, qw));
     }
     if (int rc = impc_batch_set_kernel(s.batch, IMPC_KERNEL_STRUCTURED)) {
         *no_kernel = rc == IMPC_UNSUPPORTED;
         return rc;
     }
-    RP_TRY(impc_mpc_builder_create(rp->ctx, &rp->cfg.mpc, nst, k, rp->L, &s.bld));
+    IMPC_TRY(impc_mpc_builder_create(rp->ctx, &rp->cfg.mpc, nst, k, rp->L, &s.bld));
     impc_lib::BatchInputs bi{};
-    RP_TRY(impc_lib::batch_inputs_view(s.batch, &bi));
+    IMPC_TRY(impc_lib::batch_inputs_view(s.batch, &bi));
     double *x = nullptr;
     impc_info *info = nullptr;
-    RP_TRY(impc_batch_device_results(s.batch, &x, nullptr, &info));
+    IMPC_TRY(impc_batch_device_results(s.batch, &x, nullptr, &info));
     s.dev.xws = bi.xws;
     s.dev.x = x;
     s.dev.info = info;
-    RP_TRY(impc_lib::batch_tlim_device(s.batch, &s.dev.tlim));
-    RP_TRY(rp->mem.get((size_t)std::max<int64_t>(1, cap * k), &s.dev.osrc));
+    IMPC_TRY(impc_lib::batch_tlim_device(s.batch, &s.dev.tlim));
+    IMPC_TRY(rp->mem.get((size_t)std::max<int64_t>(1, cap * k), &s.dev.osrc));
     return IMPC_OK;
 }
 
@@ -758,7 +746,7 @@ int impc_replan_create(impc_ctx ctx, const impc_replan_config *cfg, impc_replan 
         return fail(IMPC_UNSUPPORTED, "replan: the live planner path has no FOV half-spaces (num_half_space = 0)");
     if (cfg->queue_order != IMPC_QUEUE_FIFO && cfg->queue_order != IMPC_QUEUE_LONGEST_FIRST)
         return fail(IMPC_INVALID_ARGUMENT, "replan: unknown queue order");
-    RP_HIP(hipSetDevice(impc_lib::device(ctx)));
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
     std::unique_ptr<impc_replan_s> rp(new impc_replan_s());
     rp->ctx = ctx;
     rp->cfg = *cfg;
@@ -883,23 +871,23 @@ int impc_replan_set_state(impc_replan rp, const double *plan_x, const int8_t *fi
     std::vector<int32_t> pc((size_t)I);
     for (int64_t i = 0; i < I; i++) pc[(size_t)i] = ft[(size_t)i] ? 0 : (int32_t)N;  // currentStatesSol_.size()
     std::vector<int8_t> v((size_t)I, 0);
-    RP_TRY(impc_copy_to_device(rp->ctx, rp->plan_x, px.data(), (int64_t)(px.size() * 8)));
-    RP_TRY(impc_copy_to_device(rp->ctx, rp->plan_states, ps.data(), (int64_t)(ps.size() * 8)));
-    RP_TRY(impc_copy_to_device(rp->ctx, rp->first_time, ft.data(), I));
-    RP_TRY(impc_copy_to_device(rp->ctx, rp->prev_count, pc.data(), 4 * I));
-    RP_TRY(impc_copy_to_device(rp->ctx, rp->valid, v.data(), I));
+    IMPC_TRY(impc_copy_to_device(rp->ctx, rp->plan_x, px.data(), (int64_t)(px.size() * 8)));
+    IMPC_TRY(impc_copy_to_device(rp->ctx, rp->plan_states, ps.data(), (int64_t)(ps.size() * 8)));
+    IMPC_TRY(impc_copy_to_device(rp->ctx, rp->first_time, ft.data(), I));
+    IMPC_TRY(impc_copy_to_device(rp->ctx, rp->prev_count, pc.data(), 4 * I));
+    IMPC_TRY(impc_copy_to_device(rp->ctx, rp->valid, v.data(), I));
     std::vector<int32_t> rc((size_t)I, 0);  // ref_.empty()
-    RP_TRY(impc_copy_to_device(rp->ctx, rp->ref_count, rc.data(), 4 * I));
+    IMPC_TRY(impc_copy_to_device(rp->ctx, rp->ref_count, rc.data(), 4 * I));
     rp->has_state = true;
     return IMPC_OK;
 }
 
 int impc_replan_set_ref(impc_replan rp, const double *ref) {
     if (!rp || !ref) return fail(IMPC_INVALID_ARGUMENT, "replan set_ref: null object or ref");
-    RP_TRY(impc_copy_to_device(rp->ctx, rp->plan_ref, ref, (int64_t)sizeof(double) * rp->I * rp->N * 3));
+    IMPC_TRY(impc_copy_to_device(rp->ctx, rp->plan_ref, ref, (int64_t)sizeof(double) * rp->I * rp->N * 3));
     hipLaunchKernelGGL(impc_exec::k_ref_count, dim3(grid_for(rp, rp->I)), dim3(256), 0, impc_lib::stream(rp->ctx), rp->I,
                        rp->N, rp->prev_count, rp->ref_count);
-    RP_HIP(hipGetLastError());
+    HIP_OK(hipGetLastError());
     return impc_ctx_synchronize(rp->ctx);
 }
 
@@ -921,9 +909,9 @@ int impc_replan_run(impc_replan rp, const impc_replan_inputs *in) {
         return fail(IMPC_INVALID_ARGUMENT, "replan: num_static > 0 needs st_centroid, st_size, st_yaw");
     if (rp->sh.empty()) return fail(IMPC_UNSUPPORTED, kNoShapes);
     impc_ctx ctx = rp->ctx;
-    RP_HIP(hipSetDevice(impc_lib::device(ctx)));
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
     hipStream_t st = impc_lib::stream(ctx);
-    RP_TRY(impc_lib::order_after_all(ctx));
+    IMPC_TRY(impc_lib::ctx_order_after_all(ctx, st));
     const int64_t I = rp->I, n = rp->n;
     const int32_t N = rp->N, K = rp->K, L = rp->L;
 
@@ -949,49 +937,49 @@ int impc_replan_run(impc_replan rp, const impc_replan_inputs *in) {
                 rp->clk};
     const size_t lds = sizeof(int32_t) * (size_t)(2 * tile + 3) * (kPlanLanes + kPlanLanes / 64);
     hipLaunchKernelGGL(k_plan_rows, dim3((unsigned)((T + tile - 1) / tile)), dim3(kPlanLanes), lds, st, pa);
-    RP_HIP(hipGetLastError());
+    HIP_OK(hipGetLastError());
     // ---- the fan-out's closest obstacle and candidate order
     PickArgs pk{I, K, N, rp->branch, rp->num_obs, in->pos, rp->plan_states, in->dyn_cur, in->prob, rp->prev_count,
                 rp->ob, rp->ctype, rp->cslot, rp->slot_type, rp->cprob};
     hipLaunchKernelGGL(k_pick, dim3((unsigned)((I + 63) / 64)), dim3(64), 0, st, pk);
-    RP_HIP(hipGetLastError());
+    HIP_OK(hipGetLastError());
     // ---- warm starts, time limits, obstacle sources; the assembly of every shape in place
     // (timeLimit = max(solverTimeLimit_ - t, solverTimeLimit_) = solverTimeLimit_ for t >= 0, :614)
     const double tl = in->solver_time_limit > 0.0 ? in->solver_time_limit : rp->cfg.settings.time_limit;
     PrepArgs pp{I, n, rp->rows, K, L, T, rp->cnt, rp->d_sh, rp->row_inst, rp->ob, rp->slot_type, rp->row_code,
                 rp->first_time, rp->plan_x, in->prob, tl};
     hipLaunchKernelGGL(k_prep, dim3(grid_for(rp, rp->rows, 1)), dim3(64), 0, st, pp);
-    RP_HIP(hipGetLastError());
+    HIP_OK(hipGetLastError());
     for (int32_t k = 0; k < T; k++) {
         Shape &s = rp->sh[(size_t)k];
         impc_lib::BatchInputs bi{};
-        RP_TRY(impc_lib::batch_inputs_begin(s.batch, &bi));
+        IMPC_TRY(impc_lib::batch_inputs_begin(s.batch, &bi));
         const bool stat = s.nst > 0;  // its first s.nst of the instance's S_st boxes
-        RP_TRY(impc_lib::build_rows(s.bld, s.cap, rp->cnt + T + k, rp->row_inst + xshape_base(I, K, k), s.dev.osrc,
+        IMPC_TRY(impc_lib::build_rows(s.bld, s.cap, rp->cnt + T + k, rp->row_inst + xshape_base(I, K, k), s.dev.osrc,
                                     in->pos, in->vel, in->xref, rp->plan_states, in->pred_pos, in->pred_size,
                                     in->dyn_cur, in->cur_size, stat ? in->st_centroid : nullptr,
                                     stat ? in->st_size : nullptr, stat ? in->st_yaw : nullptr, rp->nst, bi, st));
-        RP_TRY(impc_lib::batch_inputs_end(s.batch, true));
+        IMPC_TRY(impc_lib::batch_inputs_end(s.batch, true));
     }
     // ---- the issue cut-off on the device clock; ONE grouped solve over every shape
     hipLaunchKernelGGL(k_issue, dim3(1), dim3(64), 0, st, T, rp->cnt, rp->solve, rp->clk, rp->issued, in->elapsed_s,
                        impc_lib::tick_s(ctx), rp->cfg.issue_cutoff_s);
-    RP_HIP(hipGetLastError());
-    RP_TRY(impc_batch_solve_group(rp->group.data(), (int)rp->group.size(), nullptr));
+    HIP_OK(hipGetLastError());
+    IMPC_TRY(impc_batch_solve_group(rp->group.data(), (int)rp->group.size(), nullptr));
     // ---- candidate validity, selection, commit
     CandArgs ca{I, n, K, L, rp->nst, rp->d_sh, rp->branch, rp->num_obs, rp->scnt, rp->slot_row, rp->cslot, rp->slot_type, rp->ob,
                 rp->issued, in->pred_pos, in->pred_size, in->prob, rp->x_cand, rp->dyn_count, rp->cvalid, rp->dyn_pos,
                 rp->dyn_size};
     hipLaunchKernelGGL(k_cand, dim3(grid_for(rp, 6 * I)), dim3(256), 0, st, ca);
     hipLaunchKernelGGL(k_sel_sets, dim3(grid_for(rp, I * 6 * (K + 1) * L)), dim3(256), 0, st, ca);
-    RP_HIP(hipGetLastError());
+    HIP_OK(hipGetLastError());
     impc_select_params sp{};
     sp.horizon = N, sp.num_candidates = 6, sp.max_dynamic = K + 1, sp.pred_len = L;
     sp.num_static = rp->nst, sp.prev_len = N;  // getTrajectoryScore's staticObstacles (:620)
     sp.dynamic_safety_dist = rp->cfg.mpc.dynamic_safety_dist;
     sp.static_safety_dist = rp->cfg.mpc.static_safety_dist;
     // (a fan-out instance is never on a first plan: scnt is its s_i, S_st without bound counts)
-    RP_TRY(impc_lib::select_best_counted(ctx, &sp, I, rp->x_cand, rp->cvalid, rp->zeros8, rp->plan_states,
+    IMPC_TRY(impc_lib::select_best_counted(ctx, &sp, I, rp->x_cand, rp->cvalid, rp->zeros8, rp->plan_states,
                                          rp->prev_count, in->xref, rp->nst ? in->st_centroid : nullptr,
                                          rp->nst ? in->st_size : nullptr, rp->nst ? rp->scnt : nullptr, rp->dyn_count,
                                          rp->dyn_pos, rp->dyn_size, rp->cprob, rp->best, rp->best_pos, rp->scores,
@@ -999,11 +987,11 @@ int impc_replan_run(impc_replan rp, const impc_replan_inputs *in) {
     CommitArgs cm{I, n, N, rp->d_sh, rp->branch, rp->shp, rp->slot_row, rp->best, rp->x_cand, rp->plan_x,
                   rp->plan_states, rp->prev_count, rp->first_time, rp->valid};
     hipLaunchKernelGGL(k_commit, dim3(grid_for(rp, I, 1)), dim3(64), 0, st, cm);
-    RP_HIP(hipGetLastError());
+    HIP_OK(hipGetLastError());
     // ---- ref_ of every committed plan (:639 / :657)
     hipLaunchKernelGGL(impc_exec::k_commit_ref, dim3(grid_for(rp, I * N * 3)), dim3(256), 0, st, I, N, rp->valid,
                        in->xref, rp->plan_ref, rp->ref_count);
-    RP_HIP(hipGetLastError());
+    HIP_OK(hipGetLastError());
     rp->ran = true;
     rp->has_state = true;
     rp->last_limit = tl;
@@ -1015,14 +1003,14 @@ int impc_replan_get_stats(impc_replan rp, impc_replan_stats *out) {
     if (!rp || !out) return fail(IMPC_INVALID_ARGUMENT, "replan: null object or output");
     std::memset(out, 0, sizeof(*out));
     if (!rp->ran) return IMPC_OK;
-    RP_TRY(impc_ctx_synchronize(rp->ctx));
+    IMPC_TRY(impc_ctx_synchronize(rp->ctx));
     const int32_t S = rp->T;
     std::vector<int64_t> c((size_t)(2 * S + 3));
     unsigned long long ck[2];
     int32_t iss = 0;
-    RP_TRY(impc_copy_to_host(rp->ctx, c.data(), rp->cnt, (int64_t)(sizeof(int64_t) * c.size())));
-    RP_TRY(impc_copy_to_host(rp->ctx, ck, rp->clk, (int64_t)sizeof(ck)));
-    RP_TRY(impc_copy_to_host(rp->ctx, &iss, rp->issued, (int64_t)sizeof(iss)));
+    IMPC_TRY(impc_copy_to_host(rp->ctx, c.data(), rp->cnt, (int64_t)(sizeof(int64_t) * c.size())));
+    IMPC_TRY(impc_copy_to_host(rp->ctx, ck, rp->clk, (int64_t)sizeof(ck)));
+    IMPC_TRY(impc_copy_to_host(rp->ctx, &iss, rp->issued, (int64_t)sizeof(iss)));
     out->fanout = c[(size_t)(2 * S + IMPC_REPLAN_FANOUT)];
     out->single_first = c[(size_t)(2 * S + IMPC_REPLAN_SINGLE_FIRST)];
     out->single_current = c[(size_t)(2 * S + IMPC_REPLAN_SINGLE_CURRENT)];
@@ -1051,8 +1039,8 @@ int shape_view(impc_replan rp, int32_t id, impc_batch *batch, int64_t *count, co
     const Shape &s = rp->sh[(size_t)id];
     int64_t c = 0;
     if (rp->ran) {
-        RP_TRY(impc_ctx_synchronize(rp->ctx));
-        RP_TRY(impc_copy_to_host(rp->ctx, &c, rp->solve + id, (int64_t)sizeof(c)));
+        IMPC_TRY(impc_ctx_synchronize(rp->ctx));
+        IMPC_TRY(impc_copy_to_host(rp->ctx, &c, rp->solve + id, (int64_t)sizeof(c)));
     }
     if (batch) *batch = s.batch;
     if (count) *count = c;
@@ -1060,7 +1048,7 @@ int shape_view(impc_replan rp, int32_t id, impc_batch *batch, int64_t *count, co
     if (row_inst) *row_inst = rp->row_inst + base;
     if (row_code) *row_code = rp->row_code + base;
     impc_lib::BatchInputs bi{};
-    RP_TRY(impc_lib::batch_inputs_view(s.batch, &bi));  // the inputs of the last assembly
+    IMPC_TRY(impc_lib::batch_inputs_view(s.batch, &bi));  // the inputs of the last assembly
     if (Px) *Px = bi.Px;
     if (q) *q = bi.q;
     if (Ax) *Ax = bi.Ax;
@@ -1075,8 +1063,8 @@ int shape_view(impc_replan rp, int32_t id, impc_batch *batch, int64_t *count, co
 // is left as it was.
 int extend_shapes(impc_replan rp) {
     impc_ctx ctx = rp->ctx;
-    RP_HIP(hipSetDevice(impc_lib::device(ctx)));
-    RP_TRY(impc_ctx_synchronize(ctx));
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
+    IMPC_TRY(impc_ctx_synchronize(ctx));
     const int64_t I = rp->I;
     const int32_t K = rp->K, S = rp->S, nst = rp->nst, T2 = S + nst * (K + 2);
     const int64_t rows2 = xshape_base(I, K, T2 - 1) + xshape_cap(I, K, T2 - 1);
@@ -1153,7 +1141,7 @@ int impc_replan_bind_static_count(impc_replan rp, const int32_t *count_device) {
     if (!rp) return fail(IMPC_INVALID_ARGUMENT, "null replan");
     if (rp->nst <= 0) return fail(IMPC_INVALID_ARGUMENT, kNoStatic);
     if (rp->sh.empty()) return fail(IMPC_UNSUPPORTED, kNoShapes);
-    if (count_device && rp->T == rp->S) RP_TRY(extend_shapes(rp));
+    if (count_device && rp->T == rp->S) IMPC_TRY(extend_shapes(rp));
     rp->scount = count_device;
     return IMPC_OK;
 }
@@ -1202,14 +1190,15 @@ int check_pack(impc_replan rp, int64_t inst_base, int32_t plan_steps, int64_t ma
 
 // k_pack_records on the context stream, after everything the replan queued
 int pack_records(impc_replan rp, int32_t rank, int64_t inst_base, int32_t plan_steps, int64_t max_inst, void *out) {
-    RP_HIP(hipSetDevice(impc_lib::device(rp->ctx)));
-    RP_TRY(impc_lib::order_after_all(rp->ctx));
+    HIP_OK(hipSetDevice(impc_lib::device(rp->ctx)));
+    hipStream_t st = impc_lib::stream(rp->ctx);
+    IMPC_TRY(impc_lib::ctx_order_after_all(rp->ctx, st));
     PackArgs pk{rp->I, max_inst, inst_base, rp->N, plan_steps, rank, rp->K, rp->nst, rp->d_sh, rp->branch, rp->valid,
                 rp->first_time, rp->prev_count, rp->best, rp->num_obs, rp->scnt, rp->ob, rp->cslot, rp->slot_row, rp->shp,
                 rp->weighted,
                 rp->plan_states, (uint64_t *)out};
-    hipLaunchKernelGGL(k_pack_records, dim3(grid_for(rp, max_inst, 1)), dim3(64), 0, impc_lib::stream(rp->ctx), pk);
-    RP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_pack_records, dim3(grid_for(rp, max_inst, 1)), dim3(64), 0, st, pk);
+    HIP_OK(hipGetLastError());
     return IMPC_OK;
 }
 
@@ -1217,31 +1206,31 @@ int pack_records(impc_replan rp, int32_t rank, int64_t inst_base, int32_t plan_s
 
 int impc_replan_pack_device(impc_replan rp, int32_t rank, int64_t inst_base, int32_t plan_steps, int64_t max_inst,
                             void *out) {
-    RP_TRY(check_pack(rp, inst_base, plan_steps, max_inst, out));
+    IMPC_TRY(check_pack(rp, inst_base, plan_steps, max_inst, out));
     return pack_records(rp, rank, inst_base, plan_steps, max_inst, out);
 }
 
 int impc_replan_gather(impc_replan rp, impc_comm comm, int64_t inst_base, int32_t plan_steps, int64_t max_inst,
                        void *recv) {
     if (!comm) return fail(IMPC_INVALID_ARGUMENT, "replan records: null communicator");
-    RP_TRY(check_pack(rp, inst_base, plan_steps, max_inst, recv));
+    IMPC_TRY(check_pack(rp, inst_base, plan_steps, max_inst, recv));
     impc_ctx cctx = nullptr;
     int rank = 0, world = 1;
-    RP_TRY(impc_lib::comm_view(comm, &cctx, &rank, &world));
+    IMPC_TRY(impc_lib::comm_view(comm, &cctx, &rank, &world));
     if (cctx != rp->ctx) return fail(IMPC_INVALID_ARGUMENT, "replan records: the communicator belongs to another context");
     // in place: this rank's block is packed where the all-gather expects it (send = recv + rank * bytes)
     const int64_t bytes = max_inst * IMPC_REPLAN_RECORD_BYTES(plan_steps);
     char *own = (char *)recv + (int64_t)rank * bytes;
-    RP_TRY(pack_records(rp, rank, inst_base, plan_steps, max_inst, own));
+    IMPC_TRY(pack_records(rp, rank, inst_base, plan_steps, max_inst, own));
     return impc_comm_allgather(comm, own, recv, bytes, nullptr);
 }
 
 int impc_replan_advance_device(impc_replan rp, double t, double *pos, double *vel) {
     if (!rp || !pos || !vel || !(t >= 0.0)) return fail(IMPC_INVALID_ARGUMENT, "replan advance: t >= 0, pos, vel");
-    RP_HIP(hipSetDevice(impc_lib::device(rp->ctx)));
+    HIP_OK(hipSetDevice(impc_lib::device(rp->ctx)));
     hipLaunchKernelGGL(k_advance, dim3(grid_for(rp, rp->I)), dim3(256), 0, impc_lib::stream(rp->ctx), rp->I, rp->N,
                        rp->n, rp->cfg.mpc.ts, t, rp->valid, rp->plan_x, pos, vel);
-    RP_HIP(hipGetLastError());
+    HIP_OK(hipGetLastError());
     return IMPC_OK;
 }
 
@@ -1268,11 +1257,11 @@ int impc_replan_target_device(impc_replan rp, const impc_target_params *p, const
     if (p->yaw_mode == IMPC_YAW_FACING && !in->facing_yaw)
         return fail(IMPC_INVALID_ARGUMENT, "replan target: IMPC_YAW_FACING needs facing_yaw");
     impc_exec::State s{};
-    RP_TRY(exec_state(rp, &s));
-    RP_HIP(hipSetDevice(impc_lib::device(rp->ctx)));
+    IMPC_TRY(exec_state(rp, &s));
+    HIP_OK(hipSetDevice(impc_lib::device(rp->ctx)));
     hipLaunchKernelGGL(impc_exec::k_target, dim3(grid_for(rp, rp->I, 1)), dim3(64), 0, impc_lib::stream(rp->ctx), s, *p,
                        *in, *out);
-    RP_HIP(hipGetLastError());
+    HIP_OK(hipGetLastError());
     return IMPC_OK;
 }
 
@@ -1286,11 +1275,11 @@ int impc_replan_check_device(impc_replan rp, const impc_check_in *in, const impc
         (!(in->map.resolution > 0.0) || in->map.dims[0] < 1 || in->map.dims[1] < 1 || in->map.dims[2] < 1))
         return fail(IMPC_INVALID_ARGUMENT, "replan check: the map needs a positive resolution and dimensions");
     impc_exec::State s{};
-    RP_TRY(exec_state(rp, &s));
-    RP_HIP(hipSetDevice(impc_lib::device(rp->ctx)));
+    IMPC_TRY(exec_state(rp, &s));
+    HIP_OK(hipSetDevice(impc_lib::device(rp->ctx)));
     hipLaunchKernelGGL(impc_exec::k_check, dim3(grid_for(rp, rp->I, 1)), dim3(64), 0, impc_lib::stream(rp->ctx), s, *in,
                        *out);
-    RP_HIP(hipGetLastError());
+    HIP_OK(hipGetLastError());
     return IMPC_OK;
 }
 

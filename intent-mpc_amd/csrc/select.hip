@@ -1,5 +1,5 @@
-// select.hpp -- device-side candidate scoring and selection (include/impc_select.h), included by
-// impc_qp.hip (same translation unit: shares the context type and error plumbing).
+// select.hip -- device-side candidate scoring and selection (include/impc_select.h), its own
+// translation unit of libimpc_qp.so (the context and the error plumbing through lib_internal.hpp).
 //
 // Two small kernels on the context stream:
 //   k_cand_scores  one thread per (instance, candidate): the three scores of getTrajectoryScore
@@ -7,7 +7,14 @@
 //   k_select       one thread per instance: evaluateTraj (mpcPlanner.cpp:850-887)
 // Work per instance is tiny (N x obstacles tanh evaluations); the point is keeping the replan's
 // solve -> score -> select on the device, next to the batched solver's outputs.
-#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/impc_select.h"
+#include "lib_internal.hpp"
+
+using impc_lib::set_error;
 
 namespace impc_select {
 
@@ -140,24 +147,28 @@ __global__ __launch_bounds__(64) void k_select(Args a) {
     a.best_pos[inst] = bestpos;
 }
 
+}  // namespace impc_select
+
 // the two kernels on `stream` (null: the context stream); st_count as Args::st_count
-int launch(impc_ctx ctx, const impc_select_params *p, int64_t instances, const double *const *x_cand,
-           const int8_t *valid, const int8_t *first_time, const double *prev_states, const int32_t *prev_count,
-           const double *xref, const double *st_centroid, const double *st_size, const int32_t *st_count,
-           const int32_t *dyn_count, const double *dyn_pos, const double *dyn_size, const double *prob,
-           int32_t *best_cand, int32_t *best_pos, double *scores, double *weighted, void *stream) {
-    if (!ctx || !p) return fail(IMPC_INVALID_ARGUMENT, "null argument");
+int impc_lib::select_best_counted(impc_ctx ctx, const impc_select_params *p, int64_t instances,
+                                  const double *const *x_cand, const int8_t *valid, const int8_t *first_time,
+                                  const double *prev_states, const int32_t *prev_count, const double *xref,
+                                  const double *st_centroid, const double *st_size, const int32_t *st_count,
+                                  const int32_t *dyn_count, const double *dyn_pos, const double *dyn_size,
+                                  const double *prob, int32_t *best_cand, int32_t *best_pos, double *scores,
+                                  double *weighted, void *stream) {
+    if (!ctx || !p) return set_error(IMPC_INVALID_ARGUMENT, "null argument");
     if (instances < 0 || p->horizon < 1 || p->num_candidates < 1 || p->num_candidates > 6 || p->max_dynamic < 0 ||
         p->pred_len < p->horizon || p->num_static < 0 || p->prev_len < 0)
-        return fail(IMPC_INVALID_ARGUMENT, "select: inconsistent sizes (1 <= C <= 6, pred_len >= horizon)");
+        return set_error(IMPC_INVALID_ARGUMENT, "select: inconsistent sizes (1 <= C <= 6, pred_len >= horizon)");
     if (instances == 0) return IMPC_OK;
-    HIP_OK(hipSetDevice(ctx->device));
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
     impc_select::Args a{instances,   p->horizon,  p->num_candidates, p->max_dynamic, p->pred_len, p->num_static,
                         p->prev_len, p->dynamic_safety_dist, p->static_safety_dist, x_cand, valid, first_time,
                         prev_states, prev_count, xref, st_centroid, st_size, dyn_count, dyn_pos, dyn_size, prob,
                         best_cand, best_pos, scores, weighted};
     a.st_count = st_count;
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t st = stream ? (hipStream_t)stream : impc_lib::stream(ctx);
     const int64_t ic = instances * p->num_candidates;
     hipLaunchKernelGGL(impc_select::k_cand_scores, dim3((unsigned)((ic + 63) / 64)), dim3(64), 0, st, a);
     HIP_OK(hipGetLastError());
@@ -166,8 +177,6 @@ int launch(impc_ctx ctx, const impc_select_params *p, int64_t instances, const d
     return IMPC_OK;
 }
 
-}  // namespace impc_select
-
 extern "C" int impc_select_best_device(impc_ctx ctx, const impc_select_params *p, int64_t instances,
                                        const double *const *x_cand, const int8_t *valid, const int8_t *first_time,
                                        const double *prev_states, const int32_t *prev_count, const double *xref,
@@ -175,9 +184,9 @@ extern "C" int impc_select_best_device(impc_ctx ctx, const impc_select_params *p
                                        const double *dyn_pos, const double *dyn_size, const double *prob,
                                        int32_t *best_cand, int32_t *best_pos, double *scores, double *weighted,
                                        void *stream) {
-    return impc_select::launch(ctx, p, instances, x_cand, valid, first_time, prev_states, prev_count, xref, st_centroid,
-                               st_size, nullptr, dyn_count, dyn_pos, dyn_size, prob, best_cand, best_pos, scores,
-                               weighted, stream);
+    return impc_lib::select_best_counted(ctx, p, instances, x_cand, valid, first_time, prev_states, prev_count, xref,
+                                         st_centroid, st_size, nullptr, dyn_count, dyn_pos, dyn_size, prob, best_cand,
+                                         best_pos, scores, weighted, stream);
 }
 
 extern "C" int impc_select_best(impc_ctx ctx, const impc_select_params *p, int64_t instances,
@@ -188,12 +197,12 @@ extern "C" int impc_select_best(impc_ctx ctx, const impc_select_params *p, int64
                                 int32_t *best_pos, double *scores, double *weighted) {
     if (!ctx || !p || !x_cand || !valid || !first_time || !prev_count || !xref || !dyn_count || !prob || !best_cand ||
         !best_pos || !scores || !weighted)
-        return fail(IMPC_INVALID_ARGUMENT, "null argument");
+        return set_error(IMPC_INVALID_ARGUMENT, "null argument");
     if ((p->prev_len > 0 && !prev_states) || (p->num_static > 0 && (!st_centroid || !st_size)) ||
         (p->max_dynamic > 0 && (!dyn_pos || !dyn_size)))
-        return fail(IMPC_INVALID_ARGUMENT, "null argument");
-    if (instances <= 0) return instances == 0 ? IMPC_OK : fail(IMPC_INVALID_ARGUMENT, "negative instance count");
-    HIP_OK(hipSetDevice(ctx->device));
+        return set_error(IMPC_INVALID_ARGUMENT, "null argument");
+    if (instances <= 0) return instances == 0 ? IMPC_OK : set_error(IMPC_INVALID_ARGUMENT, "negative instance count");
+    HIP_OK(hipSetDevice(impc_lib::device(ctx)));
     const int64_t I = instances, C = p->num_candidates, N = p->horizon;
     const size_t szx = sizeof(double *) * I * C, sz8 = I * C, szi = I, szP = sizeof(double) * I * p->prev_len * 8,
                  szpc = sizeof(int32_t) * I, szr = sizeof(double) * I * N * 8,
@@ -208,7 +217,7 @@ extern "C" int impc_select_best(impc_ctx ctx, const impc_select_params *p, int64
     }
     char *buf = nullptr;
     HIP_OK(hipMalloc((void **)&buf, total));
-    hipStream_t st = ctx->stream;
+    hipStream_t st = impc_lib::stream(ctx);
     auto up = [&](int k, const void *src) {
         return parts[k] ? hipMemcpyAsync(buf + off[k], src, parts[k], hipMemcpyHostToDevice, st) : hipSuccess;
     };
@@ -218,7 +227,7 @@ extern "C" int impc_select_best(impc_ctx ctx, const impc_select_params *p, int64
     for (int k = 0; k < 12 && e == hipSuccess; k++) e = up(k, srcs[k]);
     int rc = IMPC_OK;
     if (e != hipSuccess) {
-        rc = fail(IMPC_DEVICE_ERROR, std::string("select upload: ") + hipGetErrorString(e));
+        rc = set_error(IMPC_DEVICE_ERROR, std::string("select upload: ") + hipGetErrorString(e));
     } else {
         rc = impc_select_best_device(
             ctx, p, I, (const double *const *)(buf + off[0]), (const int8_t *)(buf + off[1]),
@@ -233,7 +242,7 @@ extern "C" int impc_select_best(impc_ctx ctx, const impc_select_params *p, int64
         for (int k = 0; k < 4 && e == hipSuccess; k++)
             e = hipMemcpyAsync(dsts[k], buf + off[12 + k], parts[12 + k], hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(IMPC_DEVICE_ERROR, std::string("select download: ") + hipGetErrorString(e));
+        if (e != hipSuccess) rc = set_error(IMPC_DEVICE_ERROR, std::string("select download: ") + hipGetErrorString(e));
     } else {
         (void)hipStreamSynchronize(st);
     }
