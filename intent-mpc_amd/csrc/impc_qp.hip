@@ -793,6 +793,16 @@ __global__ void k_expand_shared(const double *Px, const double *Ax, const int32_
         }
     }
 }
+// the launch only: what `shared` / `shared_expanded` say afterwards is the caller's (generic_setup keeps
+// the shared form for the structured kernel, a matrix update leaves it)
+int expand_shared(impc_batch b, hipStream_t st) {
+    const int64_t tot = b->B * (b->nnzP + b->nnzA);
+    const int64_t blocks = std::min<int64_t>((tot + 255) / 256, (int64_t)b->ctx->num_cu * 16);
+    hipLaunchKernelGGL(k_expand_shared, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, b->d_shPx,
+                       b->d_shAx, b->d_vmap, b->d_Axv, b->nvar, b->nnzP, b->nnzA, b->B, b->in_Px, b->in_Ax);
+    HIP_OK(hipGetLastError());
+    return IMPC_OK;
+}
 
 // ---- generic path: symbolic analysis + interleaved workspace, allocated on first use
 int ensure_generic(impc_batch b) {
@@ -877,11 +887,7 @@ int generic_setup(impc_batch b, hipStream_t st) {
     int rc = ensure_generic(b);
     if (rc) return rc;
     if (b->shared && !b->shared_expanded) {
-        const int64_t tot = b->B * (b->nnzP + b->nnzA);
-        const int64_t blocks = std::min<int64_t>((tot + 255) / 256, (int64_t)b->ctx->num_cu * 16);
-        hipLaunchKernelGGL(k_expand_shared, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, b->d_shPx,
-                           b->d_shAx, b->d_vmap, b->d_Axv, b->nvar, b->nnzP, b->nnzA, b->B, b->in_Px, b->in_Ax);
-        HIP_OK(hipGetLastError());
+        IMPC_TRY(expand_shared(b, st));
         b->shared_expanded = true;
     }
     impc::DevWork &w = b->dwk;
@@ -1088,6 +1094,46 @@ void structured_solved(impc_batch b) {
     b->persist_valid = true;
     b->rescale = b->q_after = false;
     b->has_ws = false;
+}
+
+// ---- what new inputs do to a batch's workspaces, each rule once.  An entry point that
+// puts inputs into a batch ends in values_replaced or restart, unless it is an in-place update that
+// has passed need_resumable / need_generic_setup.
+// The next structured solve does not resume the persistent workspace: it sets up from scratch.
+void clear_resume(impc_batch b) { b->persist_valid = b->q_by_update = b->rescale = b->q_after = false; }
+// ... and the generic workspace is set up again as well: what a setup read has changed
+void restart(impc_batch b) {
+    clear_resume(b);
+    b->generic_dirty = true;
+}
+// a full set of values is in the input arrays (shared: P and A in the shared-structure form)
+void values_replaced(impc_batch b, bool shared) {
+    b->shared = shared;
+    b->values_set = true;
+    restart(b);
+}
+// the in-place updates' preconditions: a persistent workspace the next structured solve resumes ...
+int need_resumable(impc_batch b) {
+    if (b->persist_on && b->persist_valid) return IMPC_OK;
+    return fail(IMPC_WORKSPACE_NOT_INIT_ERROR,
+                "structured kernel: impc_batch_set_persistent(b, 1) and one solve before updates");
+}
+// ... or a generic workspace set up on the batch's current data
+bool generic_is_set_up(impc_batch b) { return b->generic_setup_done && !b->generic_dirty; }
+int need_generic_setup(impc_batch b) {
+    return generic_is_set_up(b) ? IMPC_OK : fail(IMPC_WORKSPACE_NOT_INIT_ERROR, "setup has not run on current data");
+}
+int need_updatable(impc_batch b) { return use_structured(b) ? need_resumable(b) : need_generic_setup(b); }
+// OSQP's validate_data on host bounds [B][m]
+int check_bounds(impc_batch b, const double *l, const double *u) {
+    for (int64_t k = 0; k < b->m * b->B; k++)
+        if (l[k] > u[k]) {
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "lower bound greater than upper bound (QP %lld, row %lld)",
+                          (long long)(k / b->m), (long long)(k % b->m));
+            return fail(IMPC_DATA_VALIDATION_ERROR, msg);
+        }
+    return IMPC_OK;
 }
 
 // One batch's structured solve: a grouped launch of one entry (the entry table is cached, so
@@ -1354,7 +1400,8 @@ void reset_batch(impc_batch b) {
     b->dst.tick_s = b->ctx->tick_s;
     b->kernel_req = IMPC_KERNEL_AUTO;
     b->values_set = b->has_ws = b->ws_y = b->tlim_on = false;
-    b->persist_on = b->persist_valid = b->q_by_update = b->rescale = b->q_after = false;
+    b->persist_on = false;
+    clear_resume(b);
     b->profile = b->qpt_valid = b->ev_setup = b->ev_solve = false;
     b->queue_mode = IMPC_QUEUE_FIFO;
     b->queue_qw = 0.0;
@@ -1363,6 +1410,198 @@ void reset_batch(impc_batch b) {
     b->generic_dirty = true;
     b->generic_setup_done = b->generic_first_run = false;
     b->in_dirty = b->ws_dirty = false;
+}
+
+// ---- values into a batch, from host or from device memory: one body per entry point and its
+// _device twin.  The two primitives below carry all that differs between the twins.
+enum class Src { Host, Device };
+
+// Before input arrays are rewritten from `src`: no launch on any stream still reads them.  Host
+// sources wait on the host (their copies are synchronous anyway), device sources queue the context
+// stream, which takes their copies, after every noted launch.
+int begin_inputs(impc_batch b, Src src) {
+    return src == Src::Host ? ctx_quiesce(b->ctx) : ctx_order_after_all(b->ctx, b->ctx->stream);
+}
+// `len` doubles into an input array on the context stream: there on return (Host) or queued (Device)
+int put_input(impc_batch b, Src src, double *dst, const double *from, size_t len) {
+    if (!len) return IMPC_OK;
+    if (src == Src::Host) return h2d_sync(b->ctx->stream, dst, from, sizeof(double) * len);
+    HIP_OK(hipMemcpyAsync(dst, from, sizeof(double) * len, hipMemcpyDeviceToDevice, b->ctx->stream));
+    return IMPC_OK;
+}
+// a rewritten input array into the set-up generic workspace's interleaved copy (there on return for Host)
+int interleave_input(impc_batch b, Src src, const double *in, const double *work, int64_t len) {
+    IMPC_TRY(interleave(b, in, const_cast<double *>(work), len, b->ctx->stream));
+    if (src == Src::Host) HIP_OK(hipStreamSynchronize(b->ctx->stream));
+    return IMPC_OK;
+}
+// the generic path's in-place kernels (k_warm_start, k_update_q, k_update_bounds) on the context stream
+template <class K>
+int generic_in_place(impc_batch b, K kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(b->S / kBlock)), dim3(kBlock), 0, b->ctx->stream, b->dsym, b->dwk, b->dst,
+                       b->Bact);
+    HIP_OK(hipGetLastError());
+    return IMPC_OK;
+}
+
+int set_values(Src src, impc_batch b, const double *Px, const double *q, const double *Ax, const double *l,
+               const double *u) {
+    if (!b) return fail(IMPC_INVALID_ARGUMENT, "null batch");
+    if ((b->nnzP && !Px) || !q || (b->nnzA && !Ax) || (b->m && (!l || !u)))
+        return fail(IMPC_INVALID_ARGUMENT, "null value array");
+    if (src == Src::Host) IMPC_TRY(check_bounds(b, l, u));  // device bounds are the producer's to get right
+    HIP_OK(hipSetDevice(b->ctx->device));
+    const size_t B = (size_t)b->B;
+    const size_t len[5] = {(size_t)b->nnzP * B, (size_t)b->n * B, (size_t)b->nnzA * B, (size_t)b->m * B, (size_t)b->m * B};
+    const double *from[5] = {Px, q, Ax, l, u};
+    if (src == Src::Host && stage_ok(b)) {
+        // small batch: the five arrays packed into pinned staging (the device inputs Px, q, Ax, l, u
+        // are contiguous in that order), one DMA queued after every launch that may still read
+        // the inputs -- no host synchronisation
+        IMPC_TRY(stage_ensure(b));
+        IMPC_TRY(stage_wait(b));
+        double *s = b->h_stage;
+        for (int k = 0; k < 5; k++) {
+            if (len[k]) std::memcpy(s, from[k], sizeof(double) * len[k]);
+            s += len[k];
+        }
+        b->in_dirty = true;  // uploaded with the warm start by the next call that needs them (flush_staged)
+    } else {
+        // Both sources wait on the host here (ctx_quiesce, not begin_inputs): the device twin has
+        // always done so, and queueing its copies instead would change what its callers may overlap.
+        IMPC_TRY(ctx_quiesce(b->ctx));
+        b->in_dirty = false;  // staged inputs of an earlier host call are superseded
+        double *to[5] = {b->in_Px, b->in_q, b->in_Ax, b->in_l, b->in_u};
+        for (int k = 0; k < 5; k++) IMPC_TRY(put_input(b, src, to[k], from[k], len[k]));
+    }
+    values_replaced(b, false);
+    return IMPC_OK;
+}
+
+// A set-up generic workspace takes the warm start in place, keeping scaling, rho and factor.
+// sync_fill: the zero duals are in in_yws on return (the host call), else queued.
+int warm_start_in_place(impc_batch b, hipStream_t st, bool sync_fill) {
+    IMPC_TRY(interleave(b, b->in_xws, const_cast<double *>(b->dwk.xws), b->n, st));
+    if (!b->ws_y && b->m) {
+        const size_t bytes = sizeof(double) * b->m * b->B;
+        if (sync_fill) {
+            IMPC_TRY(fill0_sync(st, b->in_yws, bytes));
+        } else {
+            HIP_OK(hipMemsetAsync(b->in_yws, 0, bytes, st));
+        }
+    }
+    IMPC_TRY(interleave(b, b->in_yws, const_cast<double *>(b->dwk.yws), b->m, st));
+    return generic_in_place(b, k_warm_start);
+}
+
+int warm_start(Src src, impc_batch b, const double *x, const double *y) {
+    if (!b) return fail(IMPC_INVALID_ARGUMENT, "null batch");
+    HIP_OK(hipSetDevice(b->ctx->device));
+    if (!x) {
+        b->has_ws = false;
+        b->generic_dirty = true;
+        return IMPC_OK;
+    }
+    const size_t nx = (size_t)b->n * (size_t)b->B, ny = b->m && y ? (size_t)b->m * (size_t)b->B : 0;
+    if (src == Src::Host && stage_ok(b)) {  // x (and y) through the pinned staging, stream-ordered, one DMA
+        IMPC_TRY(stage_ensure(b));
+        IMPC_TRY(stage_wait(b));
+        std::memcpy(stage_xws(b), x, sizeof(double) * nx);
+        if (ny) std::memcpy(stage_xws(b) + nx, y, sizeof(double) * ny);  // in_yws follows in_xws
+        b->ws_len = nx + ny;
+        b->ws_dirty = true;  // uploaded by the next call that needs it (flush_staged)
+    } else {
+        IMPC_TRY(begin_inputs(b, src));
+        b->ws_dirty = false;  // a staged host warm start is superseded
+        IMPC_TRY(put_input(b, src, b->in_xws, x, nx));
+        // y = 0 (the solveTraj warm start, mpcPlanner.cpp:480-497): nothing is copied, the
+        // structured kernel reads no duals (WaveIO::has_ws == 2) and the generic path zero-fills
+        IMPC_TRY(put_input(b, src, b->in_yws, y, ny));
+    }
+    b->ws_y = y != nullptr;
+    // osqp_warm_start turns the warm_start setting on (osqp.c, oracle ora_warm_start)
+    b->settings.warm_start = 1;
+    b->dst.warm_start = 1;
+    if (!use_structured(b) && generic_is_set_up(b)) {
+        IMPC_TRY(flush_staged(b));
+        return warm_start_in_place(b, b->ctx->stream, src == Src::Host);
+    }
+    b->has_ws = true;
+    b->generic_dirty = true;
+    return IMPC_OK;
+}
+
+// What the in-place updates share: the checks in the order callers see them (null arguments by the
+// caller; staged values go first, the update overwrites theirs; the workspace to update exists;
+// host bounds are valid), then the wait before the input arrays are rewritten.
+int begin_update(Src src, impc_batch b, const double *l = nullptr, const double *u = nullptr) {
+    HIP_OK(hipSetDevice(b->ctx->device));
+    IMPC_TRY(flush_staged(b));
+    IMPC_TRY(need_updatable(b));
+    if (src == Src::Host && l) IMPC_TRY(check_bounds(b, l, u));
+    return begin_inputs(b, src);
+}
+
+int update_lin_cost(Src src, impc_batch b, const double *q) {
+    if (!b || !q) return fail(IMPC_INVALID_ARGUMENT, "null batch or q");
+    IMPC_TRY(begin_update(src, b));
+    IMPC_TRY(put_input(b, src, b->in_q, q, (size_t)(b->n * b->B)));
+    if (use_structured(b)) {  // the next structured solve resumes the workspace with this q
+        b->q_by_update = true;
+        b->q_after = b->rescale;
+        b->generic_dirty = true;
+        return IMPC_OK;
+    }
+    IMPC_TRY(interleave_input(b, src, b->in_q, b->dwk.q, b->n));
+    return generic_in_place(b, k_update_q);
+}
+
+int update_bounds(Src src, impc_batch b, const double *l, const double *u) {
+    if (!b || (b->m && (!l || !u))) return fail(IMPC_INVALID_ARGUMENT, "null batch or bounds");
+    IMPC_TRY(begin_update(src, b, l, u));
+    IMPC_TRY(put_input(b, src, b->in_l, l, (size_t)(b->m * b->B)));
+    IMPC_TRY(put_input(b, src, b->in_u, u, (size_t)(b->m * b->B)));
+    if (use_structured(b)) {  // the next structured solve resumes the workspace with these bounds
+        b->generic_dirty = true;
+        return IMPC_OK;
+    }
+    IMPC_TRY(interleave_input(b, src, b->in_l, b->dwk.l, b->m));
+    IMPC_TRY(interleave_input(b, src, b->in_u, b->dwk.u, b->m));
+    return generic_in_place(b, k_update_bounds);
+}
+
+// The q of the workspace at a matrix update (OSQP's scale_data normalises the cost with it; a later
+// matrix update rescales again with the q current then): kept for the next solve in case q is
+// updated before it (impc_batch_update_lin_cost after the matrices)
+int snapshot_q(impc_batch b, hipStream_t st) {
+    if (!b->d_qsnap) {
+        HIP_OK(hipMalloc((void **)&b->d_qsnap, sizeof(double) * (size_t)(b->n * b->B)));
+        b->device_bytes += (int64_t)sizeof(double) * b->n * b->B;
+    }
+    HIP_OK(hipMemcpyAsync(b->d_qsnap, b->in_q, sizeof(double) * (size_t)(b->n * b->B), hipMemcpyDeviceToDevice, st));
+    b->q_after = false;
+    return IMPC_OK;
+}
+
+int update_matrices(Src src, impc_batch b, const double *Px, const double *Ax) {
+    if (!b || (!Px && !Ax)) return fail(IMPC_INVALID_ARGUMENT, "null batch, or neither P nor A values");
+    HIP_OK(hipSetDevice(b->ctx->device));
+    IMPC_TRY(flush_staged(b));
+    if (!use_structured(b))
+        return fail(IMPC_UNSUPPORTED, "generic kernel: no in-place matrix update (impc_batch_set_values + warm start)");
+    IMPC_TRY(need_resumable(b));
+    IMPC_TRY(begin_inputs(b, src));
+    hipStream_t st = b->ctx->stream;
+    if (b->shared) {  // the kept half of the values into the per-QP arrays first
+        IMPC_TRY(expand_shared(b, st));
+        b->shared = false;
+    }
+    if (Px) IMPC_TRY(put_input(b, src, b->in_Px, Px, (size_t)(b->nnzP * b->B)));
+    if (Ax) IMPC_TRY(put_input(b, src, b->in_Ax, Ax, (size_t)(b->nnzA * b->B)));
+    IMPC_TRY(snapshot_q(b, st));
+    b->rescale = true;
+    b->generic_dirty = true;
+    return IMPC_OK;
 }
 
 uint64_t pattern_hash(int64_t n, int64_t m, int64_t batch, const int64_t *Pp, const int64_t *Pi, const int64_t *Ap,
@@ -1656,10 +1895,8 @@ int impc_batch_set_settings(impc_batch b, const impc_settings *s) {
     d.tick_s = b->ctx->tick_s;
     if (b->persist_on && s->scaling > impc::kPersistMaxScaling)
         return fail(IMPC_UNSUPPORTED, "persistent workspaces support scaling <= 20 Ruiz passes");
-    if (s->rho != b->settings.rho || s->sigma != b->settings.sigma || s->scaling != b->settings.scaling) {
-        b->generic_dirty = true;
-        b->persist_valid = b->q_by_update = b->rescale = b->q_after = false;  // a different setup: the next solve starts over
-    }
+    if (s->rho != b->settings.rho || s->sigma != b->settings.sigma || s->scaling != b->settings.scaling)
+        restart(b);  // a different setup
     b->settings = *s;
     b->dst = d;
     return IMPC_OK;
@@ -1667,52 +1904,7 @@ int impc_batch_set_settings(impc_batch b, const impc_settings *s) {
 
 int impc_batch_set_values(impc_batch b, const double *Px, const double *q, const double *Ax, const double *l,
                           const double *u) {
-    if (!b) return fail(IMPC_INVALID_ARGUMENT, "null batch");
-    if ((b->nnzP && !Px) || !q || (b->nnzA && !Ax) || (b->m && (!l || !u)))
-        return fail(IMPC_INVALID_ARGUMENT, "null value array");
-    for (int64_t k = 0; k < b->m * b->B; k++)
-        if (l[k] > u[k]) {
-            char msg[160];
-            std::snprintf(msg, sizeof msg, "lower bound greater than upper bound (QP %lld, row %lld)",
-                          (long long)(k / b->m), (long long)(k % b->m));
-            return fail(IMPC_DATA_VALIDATION_ERROR, msg);
-        }
-    HIP_OK(hipSetDevice(b->ctx->device));
-    const size_t B = (size_t)b->B;
-    if (stage_ok(b)) {
-        // small batch: the five arrays packed into pinned staging (the device inputs Px, q, Ax, l, u
-        // are contiguous in that order), one DMA queued after every launch that may still read
-        // the inputs -- no host synchronisation
-        IMPC_TRY(stage_ensure(b));
-        IMPC_TRY(stage_wait(b));
-        double *s = b->h_stage;
-        const size_t len[5] = {(size_t)b->nnzP * B, (size_t)b->n * B, (size_t)b->nnzA * B, (size_t)b->m * B,
-                               (size_t)b->m * B};
-        const double *src[5] = {Px, q, Ax, l, u};
-        for (int k = 0; k < 5; k++) {
-            if (len[k]) std::memcpy(s, src[k], sizeof(double) * len[k]);
-            s += len[k];
-        }
-        b->in_dirty = true;  // uploaded with the warm start by the next call that needs them (flush_staged)
-        b->shared = false;
-        b->persist_valid = b->q_by_update = b->rescale = b->q_after = false;
-        b->values_set = true;
-        b->generic_dirty = true;
-        return IMPC_OK;
-    }
-    IMPC_TRY(ctx_quiesce(b->ctx));  // no solve in flight on any stream reads the arrays replaced below
-    IMPC_TRY(h2d_sync(b->ctx->stream, b->in_Px, Px, sizeof(double) * b->nnzP * B));
-    IMPC_TRY(h2d_sync(b->ctx->stream, b->in_q, q, sizeof(double) * b->n * B));
-    IMPC_TRY(h2d_sync(b->ctx->stream, b->in_Ax, Ax, sizeof(double) * b->nnzA * B));
-    if (b->m) {
-        IMPC_TRY(h2d_sync(b->ctx->stream, b->in_l, l, sizeof(double) * b->m * B));
-        IMPC_TRY(h2d_sync(b->ctx->stream, b->in_u, u, sizeof(double) * b->m * B));
-    }
-    b->shared = false;
-    b->persist_valid = b->q_by_update = b->rescale = b->q_after = false;  // new data: the next solve sets up from scratch
-    b->values_set = true;
-    b->generic_dirty = true;
-    return IMPC_OK;
+    return set_values(Src::Host, b, Px, q, Ax, l, u);
 }
 
 int impc_batch_set_values_shared(impc_batch b, const double *Px, const double *Ax, int64_t nvar,
@@ -1728,13 +1920,7 @@ int impc_batch_set_values_shared(impc_batch b, const double *Px, const double *A
             return fail(IMPC_DATA_VALIDATION_ERROR, "var_pos must be ascending positions in [0, nnzA)");
         vmap[(size_t)var_pos[k]] = (int32_t)k;
     }
-    for (int64_t k = 0; k < b->m * b->B; k++)
-        if (l[k] > u[k]) {
-            char msg[160];
-            std::snprintf(msg, sizeof msg, "lower bound greater than upper bound (QP %lld, row %lld)",
-                          (long long)(k / b->m), (long long)(k % b->m));
-            return fail(IMPC_DATA_VALIDATION_ERROR, msg);
-        }
+    IMPC_TRY(check_bounds(b, l, u));
     HIP_OK(hipSetDevice(b->ctx->device));
     hipStream_t st = b->ctx->stream;
     IMPC_TRY(ctx_quiesce(b->ctx));  // no solve in flight on any stream reads the arrays replaced below
@@ -1756,88 +1942,20 @@ int impc_batch_set_values_shared(impc_batch b, const double *Px, const double *A
     IMPC_TRY(h2d_sync(st, b->d_vmap, vmap.data(), sizeof(int32_t) * vmap.size()));
     IMPC_TRY(h2d_sync(st, b->d_Axv, Ax_var, sizeof(double) * (size_t)nvar * B));
     IMPC_TRY(h2d_sync(st, b->in_q, q, sizeof(double) * b->n * B));
-    if (b->m) {
-        IMPC_TRY(h2d_sync(st, b->in_l, l, sizeof(double) * b->m * B));
-        IMPC_TRY(h2d_sync(st, b->in_u, u, sizeof(double) * b->m * B));
-    }
+    IMPC_TRY(h2d_sync(st, b->in_l, l, sizeof(double) * b->m * B));
+    IMPC_TRY(h2d_sync(st, b->in_u, u, sizeof(double) * b->m * B));
     b->nvar = nvar;
-    b->shared = true;
     b->shared_expanded = false;
-    b->persist_valid = b->q_by_update = b->rescale = b->q_after = false;
-    b->values_set = true;
-    b->generic_dirty = true;
+    values_replaced(b, true);
     return IMPC_OK;
 }
 
 int impc_batch_set_values_device(impc_batch b, const double *Px, const double *q, const double *Ax, const double *l,
                                  const double *u) {
-    if (!b) return fail(IMPC_INVALID_ARGUMENT, "null batch");
-    if ((b->nnzP && !Px) || !q || (b->nnzA && !Ax) || (b->m && (!l || !u)))
-        return fail(IMPC_INVALID_ARGUMENT, "null value array");
-    HIP_OK(hipSetDevice(b->ctx->device));
-    IMPC_TRY(ctx_quiesce(b->ctx));  // the copies below are ordered on the context stream only
-    b->in_dirty = false;            // staged inputs of impc_batch_set_values are superseded
-    hipStream_t st = b->ctx->stream;
-    const size_t B = (size_t)b->B;
-    if (b->nnzP) HIP_OK(hipMemcpyAsync(b->in_Px, Px, sizeof(double) * b->nnzP * B, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipMemcpyAsync(b->in_q, q, sizeof(double) * b->n * B, hipMemcpyDeviceToDevice, st));
-    if (b->nnzA) HIP_OK(hipMemcpyAsync(b->in_Ax, Ax, sizeof(double) * b->nnzA * B, hipMemcpyDeviceToDevice, st));
-    if (b->m) {
-        HIP_OK(hipMemcpyAsync(b->in_l, l, sizeof(double) * b->m * B, hipMemcpyDeviceToDevice, st));
-        HIP_OK(hipMemcpyAsync(b->in_u, u, sizeof(double) * b->m * B, hipMemcpyDeviceToDevice, st));
-    }
-    b->shared = false;
-    b->persist_valid = b->q_by_update = b->rescale = b->q_after = false;  // new data: the next solve sets up from scratch
-    b->values_set = true;
-    b->generic_dirty = true;
-    return IMPC_OK;
+    return set_values(Src::Device, b, Px, q, Ax, l, u);
 }
 
-int impc_batch_warm_start(impc_batch b, const double *x, const double *y) {
-    if (!b) return fail(IMPC_INVALID_ARGUMENT, "null batch");
-    HIP_OK(hipSetDevice(b->ctx->device));
-    if (!x) {
-        b->has_ws = false;
-        b->generic_dirty = true;
-        return IMPC_OK;
-    }
-    const size_t B = (size_t)b->B;
-    if (stage_ok(b)) {  // x (and y) through the pinned staging, stream-ordered, one DMA
-        IMPC_TRY(stage_ensure(b));
-        IMPC_TRY(stage_wait(b));
-        double *s = stage_xws(b);
-        std::memcpy(s, x, sizeof(double) * b->n * B);
-        if (b->m && y) std::memcpy(s + (size_t)b->n * B, y, sizeof(double) * b->m * B);  // in_yws follows in_xws
-        b->ws_len = (size_t)b->n * B + (b->m && y ? (size_t)b->m * B : 0);
-        b->ws_dirty = true;  // uploaded by the next call that needs it (flush_staged)
-    } else {
-        IMPC_TRY(ctx_quiesce(b->ctx));  // no solve in flight on any stream reads the arrays replaced below
-        IMPC_TRY(h2d_sync(b->ctx->stream, b->in_xws, x, sizeof(double) * b->n * B));
-        // y = 0 (the solveTraj warm start, mpcPlanner.cpp:480-497): nothing is uploaded, the
-        // structured kernel reads no duals (WaveIO::has_ws == 2) and the generic path zero-fills
-        if (b->m && y) IMPC_TRY(h2d_sync(b->ctx->stream, b->in_yws, y, sizeof(double) * b->m * B));
-    }
-    b->ws_y = y != nullptr;
-    // osqp_warm_start turns the warm_start setting on (osqp.c, oracle ora_warm_start)
-    b->settings.warm_start = 1;
-    b->dst.warm_start = 1;
-    if (!use_structured(b) && b->generic_setup_done && !b->generic_dirty) {
-        // a set-up generic workspace takes the warm start in place, keeping scaling, rho and factor
-        IMPC_TRY(flush_staged(b));
-        hipStream_t st = b->ctx->stream;
-        int rc = interleave(b, b->in_xws, const_cast<double *>(b->dwk.xws), b->n, st);
-        if (!rc && !b->ws_y && b->m) rc = fill0_sync(st, b->in_yws, sizeof(double) * b->m * b->B);
-        if (!rc) rc = interleave(b, b->in_yws, const_cast<double *>(b->dwk.yws), b->m, st);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_warm_start, dim3((unsigned)(b->S / kBlock)), dim3(kBlock), 0, st, b->dsym, b->dwk,
-                           b->dst, b->Bact);
-        HIP_OK(hipGetLastError());
-        return IMPC_OK;
-    }
-    b->has_ws = true;
-    b->generic_dirty = true;
-    return IMPC_OK;
-}
+int impc_batch_warm_start(impc_batch b, const double *x, const double *y) { return warm_start(Src::Host, b, x, y); }
 
 int impc_batch_set_values_async(impc_batch b, const double *Ax_var, const double *q, const double *l, const double *u,
                                 const double *x_ws, void *stream) {
@@ -1863,9 +1981,7 @@ int impc_batch_set_values_async(impc_batch b, const double *Ax_var, const double
     b->ws_y = false;
     if (x_ws) b->settings.warm_start = b->dst.warm_start = 1;
     b->shared_expanded = false;
-    b->persist_valid = b->q_by_update = b->rescale = b->q_after = false;
-    b->values_set = true;
-    b->generic_dirty = true;
+    values_replaced(b, true);  // the shared form stays (checked above)
     return IMPC_OK;
 }
 
@@ -1881,33 +1997,7 @@ int impc_batch_get_async(impc_batch b, double *x, double *y, impc_info *info, vo
 }
 
 int impc_batch_warm_start_device(impc_batch b, const double *x, const double *y) {
-    if (!b) return fail(IMPC_INVALID_ARGUMENT, "null batch");
-    HIP_OK(hipSetDevice(b->ctx->device));
-    if (!x) return impc_batch_warm_start(b, nullptr, nullptr);
-    hipStream_t st = b->ctx->stream;
-    // queued after every launch on every stream this context has used: none of them still reads
-    // the warm-start arrays when the copies land
-    IMPC_TRY(ctx_order_after_all(b->ctx, st));
-    b->ws_dirty = false;  // a staged host warm start is superseded
-    const size_t B = (size_t)b->B;
-    HIP_OK(hipMemcpyAsync(b->in_xws, x, sizeof(double) * b->n * B, hipMemcpyDeviceToDevice, st));
-    if (b->m && y) HIP_OK(hipMemcpyAsync(b->in_yws, y, sizeof(double) * b->m * B, hipMemcpyDeviceToDevice, st));
-    b->ws_y = y != nullptr;
-    b->settings.warm_start = 1;  // as impc_batch_warm_start (osqp_warm_start)
-    b->dst.warm_start = 1;
-    if (!use_structured(b) && b->generic_setup_done && !b->generic_dirty) {
-        int rc = interleave(b, b->in_xws, const_cast<double *>(b->dwk.xws), b->n, st);
-        if (!rc && !b->ws_y && b->m) HIP_OK(hipMemsetAsync(b->in_yws, 0, sizeof(double) * b->m * B, st));
-        if (!rc) rc = interleave(b, b->in_yws, const_cast<double *>(b->dwk.yws), b->m, st);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_warm_start, dim3((unsigned)(b->S / kBlock)), dim3(kBlock), 0, st, b->dsym, b->dwk,
-                           b->dst, b->Bact);
-        HIP_OK(hipGetLastError());
-        return IMPC_OK;
-    }
-    b->has_ws = true;
-    b->generic_dirty = true;
-    return IMPC_OK;
+    return warm_start(Src::Device, b, x, y);
 }
 
 int impc_batch_set_active(impc_batch b, int64_t count) {
@@ -1916,8 +2006,7 @@ int impc_batch_set_active(impc_batch b, int64_t count) {
     b->d_active = nullptr;
     if (count != b->Bact) {
         b->Bact = count;
-        b->persist_valid = b->q_by_update = b->rescale = b->q_after = false;  // the stored workspaces cover other QPs
-        b->generic_dirty = true;
+        restart(b);  // the stored workspaces cover other QPs
     }
     return IMPC_OK;
 }
@@ -2108,201 +2197,21 @@ int impc_batch_device_results(impc_batch b, double **x, double **y, impc_info **
     return IMPC_OK;
 }
 
-static int upload_interleaved(impc_batch b, const double *host, double *qp_major, double *dst, int64_t len) {
-    IMPC_TRY(h2d_sync(b->ctx->stream, qp_major, host, sizeof(double) * len * b->B));
-    int rc = interleave(b, qp_major, dst, len, b->ctx->stream);
-    if (rc) return rc;
-    HIP_OK(hipStreamSynchronize(b->ctx->stream));
-    return IMPC_OK;
-}
-
-int impc_batch_update_lin_cost(impc_batch b, const double *q) {
-    if (!b || !q) return fail(IMPC_INVALID_ARGUMENT, "null batch or q");
-    IMPC_TRY(flush_staged(b));  // the staged values go first, the update overwrites q after them
-    if (use_structured(b)) {  // the next structured solve resumes the workspace with this q
-        if (!b->persist_on || !b->persist_valid)
-            return fail(IMPC_WORKSPACE_NOT_INIT_ERROR,
-                        "structured kernel: impc_batch_set_persistent(b, 1) and one solve before updates");
-        HIP_OK(hipSetDevice(b->ctx->device));
-        IMPC_TRY(ctx_quiesce(b->ctx));
-        IMPC_TRY(h2d_sync(b->ctx->stream, b->in_q, q, sizeof(double) * b->n * b->B));
-        b->q_by_update = true;
-        b->q_after = b->rescale;
-        b->generic_dirty = true;
-        return IMPC_OK;
-    }
-    if (!b->generic_setup_done || b->generic_dirty)
-        return fail(IMPC_WORKSPACE_NOT_INIT_ERROR, "setup has not run on current data");
-    HIP_OK(hipSetDevice(b->ctx->device));
-    IMPC_TRY(ctx_quiesce(b->ctx));
-    int rc = upload_interleaved(b, q, b->in_q, const_cast<double *>(b->dwk.q), b->n);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_update_q, dim3((unsigned)(b->S / kBlock)), dim3(kBlock), 0, b->ctx->stream, b->dsym, b->dwk,
-                       b->dst, b->Bact);
-    HIP_OK(hipGetLastError());
-    return IMPC_OK;
-}
+int impc_batch_update_lin_cost(impc_batch b, const double *q) { return update_lin_cost(Src::Host, b, q); }
+int impc_batch_update_lin_cost_device(impc_batch b, const double *q) { return update_lin_cost(Src::Device, b, q); }
 
 int impc_batch_update_bounds(impc_batch b, const double *l, const double *u) {
-    if (!b || (b->m && (!l || !u))) return fail(IMPC_INVALID_ARGUMENT, "null batch or bounds");
-    IMPC_TRY(flush_staged(b));
-    if (use_structured(b)) {  // the next structured solve resumes the workspace with these bounds
-        if (!b->persist_on || !b->persist_valid)
-            return fail(IMPC_WORKSPACE_NOT_INIT_ERROR,
-                        "structured kernel: impc_batch_set_persistent(b, 1) and one solve before updates");
-        for (int64_t k = 0; k < b->m * b->B; k++)
-            if (l[k] > u[k]) return fail(IMPC_DATA_VALIDATION_ERROR, "lower bound greater than upper bound");
-        HIP_OK(hipSetDevice(b->ctx->device));
-        IMPC_TRY(ctx_quiesce(b->ctx));
-        if (b->m) {
-            IMPC_TRY(h2d_sync(b->ctx->stream, b->in_l, l, sizeof(double) * b->m * b->B));
-            IMPC_TRY(h2d_sync(b->ctx->stream, b->in_u, u, sizeof(double) * b->m * b->B));
-        }
-        b->generic_dirty = true;
-        return IMPC_OK;
-    }
-    if (!b->generic_setup_done || b->generic_dirty)
-        return fail(IMPC_WORKSPACE_NOT_INIT_ERROR, "setup has not run on current data");
-    for (int64_t k = 0; k < b->m * b->B; k++)
-        if (l[k] > u[k]) return fail(IMPC_DATA_VALIDATION_ERROR, "lower bound greater than upper bound");
-    HIP_OK(hipSetDevice(b->ctx->device));
-    IMPC_TRY(ctx_quiesce(b->ctx));
-    int rc = upload_interleaved(b, l, b->in_l, const_cast<double *>(b->dwk.l), b->m);
-    if (!rc) rc = upload_interleaved(b, u, b->in_u, const_cast<double *>(b->dwk.u), b->m);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_update_bounds, dim3((unsigned)(b->S / kBlock)), dim3(kBlock), 0, b->ctx->stream, b->dsym,
-                       b->dwk, b->dst, b->Bact);
-    HIP_OK(hipGetLastError());
-    return IMPC_OK;
+    return update_bounds(Src::Host, b, l, u);
 }
-
-int impc_batch_update_lin_cost_device(impc_batch b, const double *q) {
-    if (!b || !q) return fail(IMPC_INVALID_ARGUMENT, "null batch or q");
-    HIP_OK(hipSetDevice(b->ctx->device));
-    IMPC_TRY(flush_staged(b));
-    hipStream_t st = b->ctx->stream;
-    const size_t bytes = sizeof(double) * (size_t)(b->n * b->B);
-    if (use_structured(b)) {
-        if (!b->persist_on || !b->persist_valid)
-            return fail(IMPC_WORKSPACE_NOT_INIT_ERROR,
-                        "structured kernel: impc_batch_set_persistent(b, 1) and one solve before updates");
-        IMPC_TRY(ctx_order_after_all(b->ctx, st));
-        HIP_OK(hipMemcpyAsync(b->in_q, q, bytes, hipMemcpyDeviceToDevice, st));
-        b->q_by_update = true;
-        b->q_after = b->rescale;
-        b->generic_dirty = true;
-        return IMPC_OK;
-    }
-    if (!b->generic_setup_done || b->generic_dirty)
-        return fail(IMPC_WORKSPACE_NOT_INIT_ERROR, "setup has not run on current data");
-    IMPC_TRY(ctx_order_after_all(b->ctx, st));
-    HIP_OK(hipMemcpyAsync(b->in_q, q, bytes, hipMemcpyDeviceToDevice, st));
-    IMPC_TRY(interleave(b, b->in_q, const_cast<double *>(b->dwk.q), b->n, st));
-    hipLaunchKernelGGL(k_update_q, dim3((unsigned)(b->S / kBlock)), dim3(kBlock), 0, st, b->dsym, b->dwk, b->dst, b->Bact);
-    HIP_OK(hipGetLastError());
-    return IMPC_OK;
-}
-
 int impc_batch_update_bounds_device(impc_batch b, const double *l, const double *u) {
-    if (!b || (b->m && (!l || !u))) return fail(IMPC_INVALID_ARGUMENT, "null batch or bounds");
-    HIP_OK(hipSetDevice(b->ctx->device));
-    IMPC_TRY(flush_staged(b));
-    hipStream_t st = b->ctx->stream;
-    const size_t bytes = sizeof(double) * (size_t)(b->m * b->B);
-    if (use_structured(b)) {
-        if (!b->persist_on || !b->persist_valid)
-            return fail(IMPC_WORKSPACE_NOT_INIT_ERROR,
-                        "structured kernel: impc_batch_set_persistent(b, 1) and one solve before updates");
-        IMPC_TRY(ctx_order_after_all(b->ctx, st));
-        if (bytes) {
-            HIP_OK(hipMemcpyAsync(b->in_l, l, bytes, hipMemcpyDeviceToDevice, st));
-            HIP_OK(hipMemcpyAsync(b->in_u, u, bytes, hipMemcpyDeviceToDevice, st));
-        }
-        b->generic_dirty = true;
-        return IMPC_OK;
-    }
-    if (!b->generic_setup_done || b->generic_dirty)
-        return fail(IMPC_WORKSPACE_NOT_INIT_ERROR, "setup has not run on current data");
-    IMPC_TRY(ctx_order_after_all(b->ctx, st));
-    if (bytes) {
-        HIP_OK(hipMemcpyAsync(b->in_l, l, bytes, hipMemcpyDeviceToDevice, st));
-        HIP_OK(hipMemcpyAsync(b->in_u, u, bytes, hipMemcpyDeviceToDevice, st));
-    }
-    IMPC_TRY(interleave(b, b->in_l, const_cast<double *>(b->dwk.l), b->m, st));
-    IMPC_TRY(interleave(b, b->in_u, const_cast<double *>(b->dwk.u), b->m, st));
-    hipLaunchKernelGGL(k_update_bounds, dim3((unsigned)(b->S / kBlock)), dim3(kBlock), 0, st, b->dsym, b->dwk, b->dst,
-                       b->Bact);
-    HIP_OK(hipGetLastError());
-    return IMPC_OK;
-}
-
-// The q of the workspace at a matrix update (OSQP's scale_data normalises the cost with it; a later
-// matrix update rescales again with the q current then): kept for the next solve in case q is
-// updated before it (impc_batch_update_lin_cost after the matrices)
-static int snapshot_q(impc_batch b, hipStream_t st) {
-    if (!b->d_qsnap) {
-        HIP_OK(hipMalloc((void **)&b->d_qsnap, sizeof(double) * (size_t)(b->n * b->B)));
-        b->device_bytes += (int64_t)sizeof(double) * b->n * b->B;
-    }
-    HIP_OK(hipMemcpyAsync(b->d_qsnap, b->in_q, sizeof(double) * (size_t)(b->n * b->B), hipMemcpyDeviceToDevice, st));
-    b->q_after = false;
-    return IMPC_OK;
+    return update_bounds(Src::Device, b, l, u);
 }
 
 int impc_batch_update_matrices(impc_batch b, const double *Px, const double *Ax) {
-    if (!b || (!Px && !Ax)) return fail(IMPC_INVALID_ARGUMENT, "null batch, or neither P nor A values");
-    IMPC_TRY(flush_staged(b));
-    if (!use_structured(b))
-        return fail(IMPC_UNSUPPORTED, "generic kernel: no in-place matrix update (impc_batch_set_values + warm start)");
-    if (!b->persist_on || !b->persist_valid)
-        return fail(IMPC_WORKSPACE_NOT_INIT_ERROR,
-                    "structured kernel: impc_batch_set_persistent(b, 1) and one solve before updates");
-    HIP_OK(hipSetDevice(b->ctx->device));
-    IMPC_TRY(ctx_quiesce(b->ctx));  // no launch in flight reads the arrays replaced below
-    hipStream_t st = b->ctx->stream;
-    if (b->shared) {  // the kept half of the values into the per-QP arrays first
-        const int64_t tot = b->B * (b->nnzP + b->nnzA);
-        const int64_t blocks = std::min<int64_t>((tot + 255) / 256, (int64_t)b->ctx->num_cu * 16);
-        hipLaunchKernelGGL(k_expand_shared, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, b->d_shPx,
-                           b->d_shAx, b->d_vmap, b->d_Axv, b->nvar, b->nnzP, b->nnzA, b->B, b->in_Px, b->in_Ax);
-        HIP_OK(hipGetLastError());
-        b->shared = false;
-    }
-    if (Px && b->nnzP) IMPC_TRY(h2d_sync(st, b->in_Px, Px, sizeof(double) * b->nnzP * b->B));
-    if (Ax && b->nnzA) IMPC_TRY(h2d_sync(st, b->in_Ax, Ax, sizeof(double) * b->nnzA * b->B));
-    IMPC_TRY(snapshot_q(b, st));
-    b->rescale = true;
-    b->generic_dirty = true;
-    return IMPC_OK;
+    return update_matrices(Src::Host, b, Px, Ax);
 }
-
 int impc_batch_update_matrices_device(impc_batch b, const double *Px, const double *Ax) {
-    if (!b || (!Px && !Ax)) return fail(IMPC_INVALID_ARGUMENT, "null batch, or neither P nor A values");
-    HIP_OK(hipSetDevice(b->ctx->device));
-    IMPC_TRY(flush_staged(b));
-    if (!use_structured(b))
-        return fail(IMPC_UNSUPPORTED, "generic kernel: no in-place matrix update (impc_batch_set_values + warm start)");
-    if (!b->persist_on || !b->persist_valid)
-        return fail(IMPC_WORKSPACE_NOT_INIT_ERROR,
-                    "structured kernel: impc_batch_set_persistent(b, 1) and one solve before updates");
-    hipStream_t st = b->ctx->stream;
-    IMPC_TRY(ctx_order_after_all(b->ctx, st));  // after every launch that may still read the values
-    if (b->shared) {
-        const int64_t tot = b->B * (b->nnzP + b->nnzA);
-        const int64_t blocks = std::min<int64_t>((tot + 255) / 256, (int64_t)b->ctx->num_cu * 16);
-        hipLaunchKernelGGL(k_expand_shared, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, b->d_shPx,
-                           b->d_shAx, b->d_vmap, b->d_Axv, b->nvar, b->nnzP, b->nnzA, b->B, b->in_Px, b->in_Ax);
-        HIP_OK(hipGetLastError());
-        b->shared = false;
-    }
-    if (Px && b->nnzP)
-        HIP_OK(hipMemcpyAsync(b->in_Px, Px, sizeof(double) * b->nnzP * b->B, hipMemcpyDeviceToDevice, st));
-    if (Ax && b->nnzA)
-        HIP_OK(hipMemcpyAsync(b->in_Ax, Ax, sizeof(double) * b->nnzA * b->B, hipMemcpyDeviceToDevice, st));
-    IMPC_TRY(snapshot_q(b, st));
-    b->rescale = true;
-    b->generic_dirty = true;
-    return IMPC_OK;
+    return update_matrices(Src::Device, b, Px, Ax);
 }
 
 int impc_batch_get_stats(impc_batch b, impc_batch_stats *out) {
@@ -2366,7 +2275,7 @@ int impc_batch_set_persistent(impc_batch b, int on) {
         HIP_OK(hipMemsetAsync(b->d_persist, 0, bytes, b->ctx->stream));
     }
     b->persist_on = on != 0;
-    b->persist_valid = b->q_by_update = b->rescale = b->q_after = false;  // the next solve sets up from scratch
+    clear_resume(b);
     return IMPC_OK;
 }
 
@@ -2661,16 +2570,11 @@ int batch_inputs_begin(impc_batch b, BatchInputs *out) {
     HIP_OK(hipSetDevice(b->ctx->device));
     IMPC_TRY(ctx_order_after_all(b->ctx, b->ctx->stream));  // no launch anywhere still reads the arrays handed out
     b->in_dirty = b->ws_dirty = false;   // staged host copies are superseded
-    out->Px = b->in_Px, out->q = b->in_q, out->Ax = b->in_Ax, out->l = b->in_l, out->u = b->in_u;
-    out->xws = b->in_xws;
-    out->n = b->n, out->m = b->m, out->nnzP = b->nnzP, out->nnzA = b->nnzA, out->B = b->B;
-    return IMPC_OK;
+    return batch_inputs_view(b, out);
 }
 int batch_inputs_view(impc_batch b, BatchInputs *out) {
     if (!b || !out) return fail(IMPC_INVALID_ARGUMENT, "null batch");
-    out->Px = b->in_Px, out->q = b->in_q, out->Ax = b->in_Ax, out->l = b->in_l, out->u = b->in_u;
-    out->xws = b->in_xws;
-    out->n = b->n, out->m = b->m, out->nnzP = b->nnzP, out->nnzA = b->nnzA, out->B = b->B;
+    *out = BatchInputs{b->in_Px, b->in_q, b->in_Ax, b->in_l, b->in_u, b->in_xws, b->n, b->m, b->nnzP, b->nnzA, b->B};
     return IMPC_OK;
 }
 int batch_info_view(impc_batch b, impc_ctx *ctx, int64_t *B, const impc_info **info) {
@@ -2684,8 +2588,7 @@ int batch_set_active_device(impc_batch b, const int64_t *d_count) {
         return fail(IMPC_UNSUPPORTED, "device-side active counts need the structured kernel");
     b->d_active = d_count;
     b->Bact = b->B;
-    b->persist_valid = b->q_by_update = b->rescale = b->q_after = false;
-    b->generic_dirty = true;
+    restart(b);
     return IMPC_OK;
 }
 int batch_tlim_device(impc_batch b, double **out) {
@@ -2703,10 +2606,7 @@ int batch_tlim_device(impc_batch b, double **out) {
 double tick_s(impc_ctx ctx) { return ctx->tick_s; }
 int batch_inputs_end(impc_batch b, bool warm_x) {
     if (!b) return fail(IMPC_INVALID_ARGUMENT, "null batch");
-    b->shared = false;
-    b->persist_valid = b->q_by_update = b->rescale = b->q_after = false;  // new data: the next solve sets up from scratch
-    b->values_set = true;
-    b->generic_dirty = true;
+    values_replaced(b, false);
     b->has_ws = warm_x;
     b->ws_y = false;  // zero duals (solveTraj's warm start, mpcPlanner.cpp:480-497)
     if (warm_x) b->settings.warm_start = b->dst.warm_start = 1;
